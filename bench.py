@@ -2,7 +2,7 @@
 """V-cycle lattice-site updates per second on the 512^3 uniform 3D Poisson problem
 (BASELINE.json metric), MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 A "step" is one GMG V(1,1) cycle (GMG/Cycle.h:116-126 semantics: zero u, pre-smooth, residual,
 restrict, recurse, prolong-add, post-smooth; default options: te_cycle_opts_default, fuse = 3) over the whole 512^3 grid, 16^3 patches of 32^3
@@ -10,9 +10,14 @@ restrict, recurse, prolong-add, post-smooth; default options: te_cycle_opts_defa
 region. N > 1: one rank per GPU (torch.distributed, backend nccl == RCCL); the same 512^3
 problem is sharded by contiguous Morton ranges of patches (strong scaling).
 
-The JSON line carries `roofline` for the dominant kernel (HIP-event timed on the solver stream
-inside the timed region) and `cpu_baseline` (the CPU restatement of the reference algorithm,
-oracle/, timed on this host's cores on the same workload, bounded to ~30 s; rank 0, N = 1 only).
+A plain run sets up, runs W warm-up and K timed steps with no profiling, and prints the headline
+line (`value`, `ms_per_step`, ...). --dump-outputs DIR writes u of the last timed step as
+DIR/u.npy (a fixed sample of whole patches when it exceeds 32 MiB; see dump_outputs).
+
+With --full the JSON line also carries `roofline` for the dominant kernel (HIP-event timed on the
+solver stream inside the timed region), the per-kernel table, the secondary blocks and
+`cpu_baseline` (the CPU restatement of the reference algorithm, oracle/, timed on this host's
+cores on the same workload, bounded to ~30 s; rank 0, N = 1 only).
 `roofline.traffic` (HBM bytes per launch from rocprofv3 PMC passes) is only reported when
 profiles/traffic.json was measured on exactly the kernel sources this run compiled (a hash of
 csrc/ travels with it); otherwise it is null.
@@ -106,6 +111,12 @@ def parse():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-secondary", action="store_true", help="skip the reference-smoother block (secondary.reference_smoother)")
     ap.add_argument("--cpu-size", type=int, default=0, help="cells per axis of the CPU baseline (default: --size)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: per-kernel table and roofline (HIP events on the dominant class), median "
+                         "per-cycle time, triad ceiling, residual check, checksums, set-up times, the secondary blocks and the CPU "
+                         "baseline. Without it a run times the K steps and prints the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write u of the last step (what te_vcycle hands its caller) as DIR/u.npy (float64)")
     return ap.parse_args()
 
 
@@ -375,6 +386,33 @@ def roofline_mfma_of(name, st, dim=3, n=32):
             "flops_per_site": per_site}
 
 
+DUMP_BYTES = 32 << 20  # --dump-outputs writes at most this much of u
+
+
+def dump_outputs(path, H, u, n, dim, rank, dist):
+    """--dump-outputs: u after the last timed cycle as <path>/u.npy, float64, one row of n^dim values per patch. When all of u
+    exceeds DUMP_BYTES, a fixed sample of whole patches: numpy default_rng(0) draws patch ids from the sorted ids of level 0, and the
+    rows follow in increasing id -- the same rows for the same arguments, whatever order a build keeps its patches in. N > 1: every
+    rank downloads the sampled patches it holds, rank 0 writes the file."""
+    t = H.tables(0)
+    ids = np.sort(t["id"])
+    k = min(len(ids), max(1, DUMP_BYTES // (8 * n ** dim)))
+    pick = ids if k == len(ids) else np.sort(np.random.default_rng(0).choice(ids, size=k, replace=False))
+    where = {int(i): j for j, i in enumerate(t["id"])}
+    mine = {}
+    for i in pick:
+        j = where[int(i)]
+        if t["rank"][j] == rank:
+            mine[int(i)] = u.download_patches(int(t["local"][j]), 1)
+    if dist is not None:
+        parts = [None] * dist.get_world_size()
+        dist.all_gather_object(parts, mine)
+        mine = {i: v for p in parts for i, v in p.items()}
+    if rank == 0:
+        os.makedirs(path, exist_ok=True)
+        np.save(os.path.join(path, "u.npy"), np.stack([mine[int(i)] for i in pick]))
+
+
 def main():
     a = parse()
     # stdout carries exactly one JSON line: everything else that libraries print there (e.g. Gloo's connection
@@ -534,6 +572,9 @@ def run(a, json_out, rank, world, local_rank):
     u = g.new_vector(0)
     g0, f0, u0 = g, f, u
     cells_global = [H.sizes(l)[1] * n ** a.dim for l in range(H.num_levels)]
+    workload = (f"apps/{a.dim}d/steady-equivalent: " + (f"{os.path.basename(a.mesh)} --divide {a.divide}" if a.mesh else f"{a.size}^{a.dim} uniform")
+                + f", {cells_global[0] // n ** a.dim} patches of {n}^{a.dim}, {H.num_levels} levels, V(1,1), smoother={a.smoother}, "
+                "Dirichlet, f ~ U(-1,1) splitmix64(0x5EED + patch id)")
     # this rank's sites in patches that copy through to the next level, summed over the levels (refined meshes only)
     copy_sites = 0
     if a.mesh:
@@ -552,11 +593,28 @@ def run(a, json_out, rank, world, local_rank):
             dist.barrier()
             torch.cuda.synchronize()
 
-    def measure(o, steps, warmup, g=None, f=None, u=None):
+    def max_over_ranks(dt):
+        if dist is not None:
+            tt = torch.tensor([dt], dtype=torch.float64, device=red_dev)
+            dist.all_reduce(tt, op=dist.ReduceOp.MAX)
+            dt = float(tt.item())
+        return dt
+
+    def measure(o, steps, warmup, g=None, f=None, u=None, profiled=True):
         """W untimed warm-up cycles with every kernel class timed (per-kernel table; names the dominant class), then
         exactly K cycles between two barriers with HIP events on the dominant class only; max over ranks
-        (g, f, u: another solver and its vectors -- the problem-size block; default: the headline's)"""
+        (g, f, u: another solver and its vectors -- the problem-size block; default: the headline's).
+        profiled=False (a run without --full): the same W and K cycles with no profiling at all"""
         g, f, u = (g0 if g is None else g), (f0 if f is None else f), (u0 if u is None else u)
+        if not profiled:
+            for _ in range(warmup):
+                g.cycle(o, f, u)
+            barrier()
+            t0 = time.perf_counter()
+            for _ in range(steps):
+                g.cycle(o, f, u)
+            barrier()
+            return {"dt": max_over_ranks(time.perf_counter() - t0)}
         g.profile(True)
         g.profile_select(None)
         # the very first step pays one-time costs (code load, lazy attributes): its events are dropped, so the table
@@ -602,11 +660,7 @@ def run(a, json_out, rank, world, local_rank):
         g.profile(False)
         g.profile_select(None)
         g.profile_stride(1)
-        if dist is not None:
-            tt = torch.tensor([dt], dtype=torch.float64, device=red_dev)
-            dist.all_reduce(tt, op=dist.ReduceOp.MAX)
-            dt = float(tt.item())
-        return {"dt": dt, "rows_all": rows_all, "rows": rows, "profiled_warm": profiled_warm, "event_stride": stride}
+        return {"dt": max_over_ranks(dt), "rows_all": rows_all, "rows": rows, "profiled_warm": profiled_warm, "event_stride": stride}
 
     def median_cycle_ms(o, steps, g=None, f=None, u=None):
         """median of per-cycle times: an event pair per cycle on the solver stream"""
@@ -645,11 +699,29 @@ def run(a, json_out, rank, world, local_rank):
             c = (lo + (hi << 32)) & 0xFFFFFFFFFFFFFFFF
         return f"{c:016x}"
 
-    m = measure(opts, a.steps, a.warmup)
-    dt, rows_all, rows = m["dt"], m["rows_all"], m["rows"]
-    u_checksum = checksum(u)  # (every cycle of the timed region starts from u = 0 on the same f: this is the result of ONE cycle)
+    m = measure(opts, a.steps, a.warmup, profiled=a.full)
+    dt = m["dt"]
     ms_per_step = dt / a.steps * 1e3
     value = cells_global[0] / (dt / a.steps)
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, H, u, n, a.dim, rank, dist)
+    if not a.full:
+        # the headline and nothing else: what --full adds beside it takes runs of its own
+        if rank == 0:
+            print(json.dumps({
+                "metric": metric_name(a),
+                "value": value, "unit": "lattice-site updates/s", "n_gpus": world, "steps": a.steps,
+                "warmup": a.warmup, "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "strong",
+                "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+                "config": {"workload": workload, "workload_key": workload_key(a), "parallelism": f"patch-sharded x{world} (Morton ranges)",
+                           "exchange": exchange_backend, "levels": H.num_levels, "autotune": autotune, "smoother": a.smoother}}),
+                  file=json_out, flush=True)
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+    rows_all, rows = m["rows_all"], m["rows"]
+    u_checksum = checksum(u)  # (every cycle of the timed region starts from u = 0 on the same f: this is the result of ONE cycle)
     # median of per-cycle times: a second, untimed-by-the-contract pass with an event pair per cycle on
     # the solver stream (`value` above stays the contract's K steps between two synchronisations)
     ms_median = median_cycle_ms(opts, a.steps)
@@ -726,9 +798,7 @@ def run(a, json_out, rank, world, local_rank):
             # the single-rank cycle by construction, so the lines of N = 1, 2, 4, 8 on the same workload must carry the SAME value --
             # SURVEY 8(e)'s equality test, run by whoever runs the scaling bench
             "u_checksum_after_timed_region": u_checksum,
-            "config": {"workload": f"apps/{a.dim}d/steady-equivalent: " + (f"{os.path.basename(a.mesh)} --divide {a.divide}" if a.mesh else f"{a.size}^{a.dim} uniform") + f", {cells_global[0] // n ** a.dim} "
-                                   f"patches of {n}^{a.dim}, {H.num_levels} levels, V(1,1), smoother={a.smoother}, "
-                                   "Dirichlet, f ~ U(-1,1) splitmix64(0x5EED + patch id)",
+            "config": {"workload": workload,
                        "workload_key": workload_key(a),
                        # what carried the exchanges of the timed region (N > 1)
                        "parallelism": f"patch-sharded x{world} (Morton ranges)", "exchange": exchange_backend,

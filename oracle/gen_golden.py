@@ -11,6 +11,7 @@ reference); the .npz files are committed, this script is how they were made:
 
     make -C oracle -f Makefile.ref
     LD_LIBRARY_PATH=/usr/lib/x86_64-linux-gnu:/opt/conda/lib python oracle/gen_golden.py
+    ... python oracle/gen_golden.py live    # tests/golden/slice_live_*.npz only
 """
 import ctypes as C
 import os
@@ -92,7 +93,23 @@ def vecop_case(seed):
     return out
 
 
+# tests/test_oracle_golden.py::test_live_against_reference_slice: its seeded inputs on the levels of tests/util.py, and the slice's outputs
+LIVE_CASES = [("3uni.bin", 4, 0), ("2refine.bin", 4, 1), ("2d2ref.bin", 8, 1)]
+
+
+def live_case(mesh_file, n, div):
+    from tests import util
+    _, _, levels = util.setup(mesh_file, n, div, dim=2 if mesh_file.startswith("2d") else 3)
+    L = levels[0]
+    u = util.rand_vec(L.size, 77)
+    return dict(u=u, interp=refslice.interp(L, u), apply=refslice.apply(L, u), patch_apply=refslice.patch_apply(L, u))
+
+
 def main():
+    if sys.argv[1:] == ["live"]:
+        for mf, n, div in LIVE_CASES:
+            np.savez_compressed(os.path.join(GOLDEN, f"slice_live_{mf.split('.')[0]}_n{n}_div{div}.npz"), **live_case(mf, n, div))
+        return
     cases = [("2uni.bin", 3, 4, False), ("2uni.bin", 3, 8, False), ("2refine.bin", 3, 4, False),
              ("2refine.bin", 3, 8, False), ("2refine.bin", 3, 4, True), ("1uni.bin", 3, 8, True),
              ("2d2uni.bin", 2, 8, False), ("2d2ref.bin", 2, 8, False), ("2d2ref.bin", 2, 4, True)]

@@ -97,7 +97,7 @@ def test_in_process_headline_survives_any_exception_behind_it():
 def test_optional_block_that_raises_leaves_its_error_under_its_own_name():
     """on the GPU box, the real thing at N = 1: secondary.reference_smoother raises a ValueError; the line keeps its value, carries
     secondary.reference_smoother.error, and the blocks behind it (secondary.solve) still ran"""
-    p = run_bench(["--gpus", "1", "--size", "128", "--steps", "3", "--warmup", "2", "--no-cpu-baseline"], {"TE_BENCH_TEST_RAISE": "reference_smoother"})
+    p = run_bench(["--gpus", "1", "--size", "128", "--steps", "3", "--warmup", "2", "--full", "--no-cpu-baseline"], {"TE_BENCH_TEST_RAISE": "reference_smoother"})
     assert p.returncode == 0, p.stderr[-3000:]
     out = json_lines(p.stdout)[-1]
     assert out["value"] > 0 and "error" not in out
@@ -111,7 +111,7 @@ def test_self_launch_two_ranks_gloo_rehearsal():
     computed: u_checksum_after_timed_region equals the N = 1 line's on the same workload (sharded == single rank, bit for bit),
     the other transport (direct stores between the two processes, hipIpc) reproduced the headline transport's result bit for
     bit (config.sharded.verified_bit_identical) and is reported as a SECOND figure, config.exchange names what carried `value`"""
-    args = ["--steps", "3", "--warmup", "2", "--size", "128", "--no-cpu-baseline"]
+    args = ["--steps", "3", "--warmup", "2", "--size", "128", "--full", "--no-cpu-baseline"]
     p = run_bench(["--gpus", "2"] + args, {"TE_BENCH_BACKEND": "gloo"})
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
@@ -130,3 +130,71 @@ def test_self_launch_two_ranks_gloo_rehearsal():
     assert ds["u_checksum"] == ds["u_checksum_headline_transport"] == out["u_checksum_after_timed_region"]
     assert out["config"]["sharded"]["verified_bit_identical"]["identical"] is True
     assert out["secondary"]["solve"]["rbgs"]["x_checksum"]
+
+
+def test_dump_outputs_writes_a_fixed_bounded_sample(tmp_path, monkeypatch):
+    """--dump-outputs, without a GPU (stand-ins for the hierarchy and u): whole patches, one row each, in increasing patch id; the
+    same rows whatever order a build keeps its patches in; at most bench.DUMP_BYTES (and the cap stays under 64 MB); all of u
+    when it fits"""
+    import numpy as np
+    import bench
+    assert bench.DUMP_BYTES <= 64e6
+    n, dim, P = 8, 3, 4096
+    nc = n ** dim
+
+    class H:
+        def __init__(self, ids):
+            self.ids = ids
+
+        def tables(self, level):
+            assert level == 0
+            return {"id": self.ids, "rank": np.zeros(P, np.int32), "local": np.arange(P, dtype=np.int32)}
+
+    class U:
+        def __init__(self, ids):
+            self.ids = ids
+
+        def download_patches(self, first, count):
+            assert count == 1 and 0 <= first < P
+            return np.arange(nc) + 1000.0 * self.ids[first]
+
+    def dump(ids, name):
+        bench.dump_outputs(str(tmp_path / name), H(ids), U(ids), n, dim, 0, None)
+        return np.load(tmp_path / name / "u.npy")
+
+    ids = (np.random.default_rng(7).permutation(P) * 3 + 5).astype(np.int32)  # not 0..P-1 and not in order
+    monkeypatch.setattr(bench, "DUMP_BYTES", 64 * 8 * nc)
+    a = dump(ids, "a")
+    assert a.dtype == np.float64 and a.shape == (64, nc) and a.nbytes <= bench.DUMP_BYTES
+    rows = (a[:, 0] / 1000.0).astype(np.int64)
+    assert np.all(np.diff(rows) > 0) and np.all(np.isin(rows, ids)) and np.array_equal(a, rows[:, None] * 1000.0 + np.arange(nc))
+    assert np.array_equal(dump(ids[::-1].copy(), "b"), a)
+    monkeypatch.setattr(bench, "DUMP_BYTES", P * 8 * nc)
+    c = dump(ids, "c")
+    assert np.array_equal((c[:, 0] / 1000.0).astype(np.int64), np.sort(ids))
+
+
+@pytest.mark.gpu
+def test_plain_run_is_the_headline_and_dumps_the_timed_result(tmp_path):
+    """without --full: one line with the headline's keys and nothing that takes runs of its own; --dump-outputs writes u of the
+    last timed cycle -- at 128^3 (64 patches) all of it: its te_vec_checksum is the u_checksum_after_timed_region of a --full run
+    on the same arguments, and the two dumps are identical (same inputs, same result)"""
+    import numpy as np
+    args = ["--gpus", "1", "--size", "128", "--steps", "3", "--warmup", "1"]
+    p = run_bench(args + ["--dump-outputs", str(tmp_path / "plain")], {})
+    assert p.returncode == 0, p.stderr[-3000:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, p.stdout
+    out = json.loads(lines[0])
+    assert out["steps"] == 3 and out["warmup"] == 1 and out["n_gpus"] == 1 and out["value"] > 0 and "error" not in out
+    assert out["unit"] == "lattice-site updates/s" and out["higher_is_better"] is True and out["dtype"] == "f64"
+    assert abs(out["value"] - 128 ** 3 / (out["ms_per_step"] * 1e-3)) <= 1e-9 * out["value"]
+    assert not {"roofline", "kernels_warmup", "secondary", "cpu_baseline", "ms_per_step_median", "setup_ms"} & set(out)
+    u = np.load(tmp_path / "plain" / "u.npy")
+    assert u.dtype == np.float64 and u.shape == (64, 32 ** 3) and np.all(np.isfinite(u)) and np.abs(u).max() > 0
+    q = run_bench(args + ["--full", "--no-secondary", "--no-cpu-baseline", "--dump-outputs", str(tmp_path / "full")], {})
+    assert q.returncode == 0, q.stderr[-3000:]
+    full = json_lines(q.stdout)[-1]
+    assert full["steps"] == 3 and "roofline" in full and "kernels_warmup" in full
+    assert np.array_equal(np.load(tmp_path / "full" / "u.npy"), u)
+    assert f"{int(u.view(np.uint64).sum(dtype=np.uint64)):016x}" == full["u_checksum_after_timed_region"]

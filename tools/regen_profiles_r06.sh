@@ -24,7 +24,7 @@ python3 tools/mr8_budget.py --size 512 --smoother rbgs --agg 64 --out ${W}_mr8_b
 python3 tools/mr8_budget.py --size 512 --smoother rbgs --agg 64 --push --ranks 2,4,8 --out ${W}_mr8_budget_push.txt > /dev/null 2>> ${W}_mr8.err && echo "mr8 push ok"
 python3 tools/mr8_budget.py --size 512 --smoother patch_solve --agg 64 --ranks 1,8 --out ${W}_mr8_budget_ps.txt > /dev/null 2>> ${W}_mr8.err && echo "mr8 ps ok"
 python3 tools/mr8_budget.py --dim 2 --size 4096 --agg 64 --ranks 1,8 --out ${W}_mr8_budget_2d.txt > /dev/null 2>> ${W}_mr8.err && echo "mr8 2d ok"
-python3 bench.py --steps 10 --warmup 3 --size 1024 --no-cpu-baseline > ${W}_bench_1024.json 2>> ${W}_bench_512.err && echo "1024 ok"
-TE_BENCH_BACKEND=gloo timeout -k 10 600 python3 bench.py --gpus 4 --size 512 > ${W}_rehearsal_512_n4.json 2> ${W}_rehearsal.err && echo "rehearsal 512 ok"
-TE_BENCH_BACKEND=gloo timeout -k 10 600 python3 bench.py --gpus 4 --size 1024 --no-cpu-baseline > ${W}_rehearsal_1024_n4.json 2>> ${W}_rehearsal.err && echo "rehearsal 1024 ok"
+python3 bench.py --full --steps 10 --warmup 3 --size 1024 --no-cpu-baseline > ${W}_bench_1024.json 2>> ${W}_bench_512.err && echo "1024 ok"
+TE_BENCH_BACKEND=gloo timeout -k 10 600 python3 bench.py --full --gpus 4 --size 512 > ${W}_rehearsal_512_n4.json 2> ${W}_rehearsal.err && echo "rehearsal 512 ok"
+TE_BENCH_BACKEND=gloo timeout -k 10 600 python3 bench.py --full --gpus 4 --size 1024 --no-cpu-baseline > ${W}_rehearsal_1024_n4.json 2>> ${W}_rehearsal.err && echo "rehearsal 1024 ok"
 echo "all done"
