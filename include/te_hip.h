@@ -84,6 +84,12 @@ int te_hier_level_tables(const te_hier *h, int level, int32_t *id, int32_t *rank
                          int32_t *nbr_orth, int32_t *parent, int32_t *orth_on_parent);
 /* local -> global patch index of this rank's patches */
 int  te_hier_level_l2g(const te_hier *h, int level, int32_t *l2g);
+/* The interfaces of a level, the unknowns of the Schur-complement route: SchurHelper<D>::indexDomainIfacesLocal
+ * (SchurHelper.h:377-397), the first-seen order of SchurInfo<D>::getIds() over the patches in this library's order.
+ * iface_index[P][2*dim] = the interface patch p sees on side s, -1 on a physical face. Single-rank hierarchies only
+ * (TE_ESTATE on a sharded one). */
+int  te_hier_num_ifaces(const te_hier *h, int level, int *num_ifaces);
+int  te_hier_iface_index(const te_hier *h, int level, int32_t *iface_index);
 void te_hier_destroy(te_hier *h);
 
 /* ------------------------------------------------------------------------ device objects */
@@ -133,6 +139,11 @@ void *te_gmg_stream(te_gmg *g);         /* hipStream_t, for event timing by the 
 
 /* VectorGenerator<D>::getNewVector (Vector.h:323-327; DomainVG Domain.h:415-429): zero-filled */
 int    te_vec_create(te_gmg *g, int level, te_vec **out);
+/* SchurHelper<D>::getNewSchurVec (SchurHelper.h:156-160): an interface vector of `level`, num_ifaces * n^(dim-1) doubles,
+ * one block per interface (te_hier_num_ifaces), zero-filled. Every te_vec_* call takes it (te_vec_upload_patches /
+ * te_vec_download_patches count interface blocks instead of patches); the domain operators (te_apply, te_smooth, te_vcycle,
+ * te_bicgstab, ...) refuse it with TE_EINVAL. Single rank: TE_ESTATE on a sharded hierarchy. */
+int    te_vec_create_iface(te_gmg *g, int level, te_vec **out);
 void   te_vec_destroy(te_vec *v);
 size_t te_vec_size(const te_vec *v);                 /* doubles (local patches * n^dim) */
 int    te_vec_upload(te_vec *v, const double *host); /* Vector<D>::getLocalData write path */
@@ -288,6 +299,35 @@ int te_gmg_exchange_selftest(te_gmg *g, int n);
  * its deadline from the first exchange instead of the oldest OUTSTANDING one would end the process with status 86 here
  * once `seconds` exceeds TE_EXCHANGE_TIMEOUT. With one rank the watchdog runs only when TE_EXCHANGE_TIMEOUT is set. */
 int te_gmg_watchdog_selftest(te_gmg *g, double seconds);
+
+/* ------------------------------------------------ Schur-complement interface route (single rank) */
+/* The reference's second way to the same discrete system (apps/3d/steady.cpp:336-420, apps/2d/steady.cpp:383-480 with
+ * --schur): a Krylov method on the interface values gamma alone. With Solve(f, gamma) the exact patch solves of StarPatchOp
+ * with right-hand side f - 2 gamma / h^2 on the face layers and Interp the interpolation to the interfaces:
+ *   T gamma = Interp(Solve(0, gamma)),  S = I - T,  g = Interp(Solve(f, 0));  S gamma* = g,  u = Solve(f, gamma*) solves A u = f.
+ * gamma / x / y are interface vectors (te_vec_create_iface), u / f domain vectors, all of `level`. Every call returns TE_ESTATE
+ * on a sharded hierarchy. DESIGN.md "Schur-complement route" has the kernels. */
+/* SchurHelper<D>::interpolateToInterface (SchurHelper.h:333-343): gamma = Interp(u) */
+int te_iface_interp(te_gmg *g, int level, const te_vec *u, te_vec *gamma);
+/* SchurHelper<D>::applyWithInterface (SchurHelper.h:344-359, StarPatchOp.h:28-184): f = A_patch u with the interface
+ * values gamma on every face that has a neighbour */
+int te_apply_with_interface(te_gmg *g, int level, const te_vec *u, const te_vec *gamma, te_vec *f);
+/* PatchOperator<D>::addInterfaceToRHS (StarPatchOp.h:185-203), in place: f -= 2 gamma / h^2 on the face layers */
+int te_add_iface_rhs(te_gmg *g, int level, const te_vec *gamma, te_vec *f);
+/* SchurHelper<D>::solveWithInterface (SchurHelper.h:280-297): u = Solve(f, gamma); diff (may be NULL) = Interp(u) - gamma */
+int te_solve_with_interface(te_gmg *g, int level, const te_vec *f, te_vec *u, const te_vec *gamma, te_vec *diff);
+/* Operators/SchurWrapOp.h with the identity term the Schur system needs: y = x - T x (x and y distinct) */
+int te_schur_apply(te_gmg *g, int level, const te_vec *x, te_vec *y);
+/* PolyChebPrec::apply (PolyChebPrec.cpp): y = p(T) x, p the degree-15 Chebyshev approximation of 1 / (1 - t) on
+ * [0, 0.95] (coefficients from their closed form), by the same Clenshaw recurrence: an approximation of S^-1 */
+int te_schur_cheb(te_gmg *g, int level, const te_vec *x, te_vec *y);
+#define TE_SCHUR_PREC_NONE 0
+#define TE_SCHUR_PREC_CHEB 1
+/* BiCGStab<D-1>::solve (BiCGStab.h:45-106, the statements of te_bicgstab) on S gamma = g, right-preconditioned by `prec`;
+ * gamma = the initial guess on entry, the solution on exit; then u = Solve(f, gamma). Stops when ||r|| / ||r0|| <= tol
+ * or after max_it iterations. A level without interfaces (one patch) takes 0 iterations: u = Solve(f, -). */
+int te_schur_solve(te_gmg *g, int level, int prec, const te_vec *f, te_vec *u, te_vec *gamma, int max_it, double tol,
+                   int *iterations, double *rel_resid);
 
 /* Domain<D>::integrate (Domain.h:258-278) and Domain<D>::volume (:237-251), this rank's part (the host adds the
  * ranks as it does for norms): sum over local patches of (sum of the patch's cells) * (cell volume), resp. of the

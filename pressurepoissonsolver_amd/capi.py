@@ -29,6 +29,7 @@ class TeLibraryMissing(ImportError):
 TE_OK, TE_EINVAL, TE_EHIP, TE_ESTATE, TE_EIO, TE_EUNSUPPORTED, TE_ENOMEM = 0, -1, -2, -3, -4, -5, -6
 SMOOTH_PATCH_SOLVE, SMOOTH_JACOBI, SMOOTH_RBGS, SMOOTH_PATCH_BCGS = 0, 1, 2, 3
 PROBLEM_TRIG, PROBLEM_GAUSS, PROBLEM_RANDOM = 0, 1, 2
+SCHUR_PREC_NONE, SCHUR_PREC_CHEB = 0, 1
 
 
 class CycleOpts(C.Structure):
@@ -72,6 +73,8 @@ SYMBOLS = {
     "te_hier_level_replicated": (_I, [_P, _I]),
     "te_hier_level_tables": (_I, [_P, _I] + [_P] * 10),
     "te_hier_level_l2g": (_I, [_P, _I, _P]),
+    "te_hier_num_ifaces": (_I, [_P, _I, C.POINTER(_I)]),
+    "te_hier_iface_index": (_I, [_P, _I, _P]),
     "te_hier_destroy": (None, [_P]),
     "te_cycle_opts_default": (None, [C.POINTER(CycleOpts)]),
     "te_gmg_create": (_I, [_P, _I, C.POINTER(_P)]),
@@ -80,6 +83,7 @@ SYMBOLS = {
     "te_gmg_sync": (_I, [_P]),
     "te_gmg_stream": (_P, [_P]),
     "te_vec_create": (_I, [_P, _I, C.POINTER(_P)]),
+    "te_vec_create_iface": (_I, [_P, _I, C.POINTER(_P)]),
     "te_vec_destroy": (None, [_P]),
     "te_vec_size": (C.c_size_t, [_P]),
     "te_vec_upload": (_I, [_P, _P]),
@@ -132,6 +136,13 @@ SYMBOLS = {
     "te_gmg_profile_select": (_I, [_P, C.c_char_p]),
     "te_gmg_profile_stride": (_I, [_P, _I]),
     "te_init_problem": (_I, [_P, _I, _I, _I, _P, _P]),
+    "te_iface_interp": (_I, [_P, _I, _P, _P]),
+    "te_apply_with_interface": (_I, [_P, _I, _P, _P, _P]),
+    "te_add_iface_rhs": (_I, [_P, _I, _P, _P]),
+    "te_solve_with_interface": (_I, [_P, _I, _P, _P, _P, _P]),
+    "te_schur_apply": (_I, [_P, _I, _P, _P]),
+    "te_schur_cheb": (_I, [_P, _I, _P, _P]),
+    "te_schur_solve": (_I, [_P, _I, _I, _P, _P, _P, _I, _D, C.POINTER(_I), _PD]),
     "te_integrate": (_I, [_P, _I, _P, _P]),
     "te_volume": (_I, [_P, _I, _P]),
 }
@@ -278,6 +289,18 @@ class Hierarchy:
             "orth_on_parent")]))
         return t
 
+    def num_ifaces(self, level=0):
+        """interfaces of the level (SchurHelper.h:377-397); single-rank hierarchies only"""
+        out = C.c_int()
+        check(lib().te_hier_num_ifaces(self.h, level, C.byref(out)))
+        return out.value
+
+    def iface_index(self, level=0):
+        """[P][2*dim] the interface patch p sees on side s, -1 on a physical face"""
+        out = np.zeros((self.sizes(level)[1], 2 * self.dim), np.int32)
+        check(lib().te_hier_iface_index(self.h, level, _ptr(out)))
+        return out
+
     def l2g(self, level):
         out = np.zeros(self.sizes(level)[0], np.int32)
         check(lib().te_hier_level_l2g(self.h, level, _ptr(out)))
@@ -295,10 +318,11 @@ class Hierarchy:
 class Vec:
     """Vector<D> on the device (Vector.h:179-321); method names follow the reference."""
 
-    def __init__(self, gmg, level=0, data=None):
-        self.gmg, self.level = gmg, level
+    def __init__(self, gmg, level=0, data=None, iface=False):
+        """iface: an interface vector of the level (SchurHelper::getNewSchurVec), one block of n^(dim-1) per interface"""
+        self.gmg, self.level, self.iface = gmg, level, iface
         self.h = C.c_void_p()
-        check(lib().te_vec_create(gmg.h, level, C.byref(self.h)))
+        check((lib().te_vec_create_iface if iface else lib().te_vec_create)(gmg.h, level, C.byref(self.h)))
         if data is not None:
             self.upload(data)
 
@@ -320,13 +344,13 @@ class Vec:
     def upload_patches(self, first, a):
         """Vector<D>::getLocalData(i) write path for a run of patches"""
         a = np.ascontiguousarray(a, dtype=np.float64)
-        nc = self.gmg.hier.n ** self.gmg.hier.dim
+        nc = self.gmg.hier.n ** (self.gmg.hier.dim - self.iface)
         if a.size % nc:
             raise ValueError("upload_patches: not a whole number of patches")
         check(lib().te_vec_upload_patches(self.h, first, a.size // nc, _ptr(a.ravel())))
 
     def download_patches(self, first, count):
-        out = np.empty(count * self.gmg.hier.n ** self.gmg.hier.dim, np.float64)
+        out = np.empty(count * self.gmg.hier.n ** (self.gmg.hier.dim - self.iface), np.float64)
         check(lib().te_vec_download_patches(self.h, first, count, _ptr(out)))
         return out
 
@@ -409,6 +433,26 @@ class GMG:
 
     def new_vector(self, level=0, data=None):
         return Vec(self, level, data)
+
+    def new_iface_vector(self, level=0, data=None):
+        return Vec(self, level, data, iface=True)
+
+    # ---- the Schur-complement route (SchurHelper.h), single rank
+    def iface_interp(self, u, gamma, level=0): check(lib().te_iface_interp(self.h, level, u.h, gamma.h))
+    def apply_with_interface(self, u, gamma, f, level=0): check(lib().te_apply_with_interface(self.h, level, u.h, gamma.h, f.h))
+    def add_iface_rhs(self, gamma, f, level=0): check(lib().te_add_iface_rhs(self.h, level, gamma.h, f.h))
+
+    def solve_with_interface(self, f, u, gamma, diff=None, level=0):
+        check(lib().te_solve_with_interface(self.h, level, f.h, u.h, gamma.h, diff.h if diff is not None else None))
+
+    def schur_apply(self, x, y, level=0): check(lib().te_schur_apply(self.h, level, x.h, y.h))
+    def schur_cheb(self, x, y, level=0): check(lib().te_schur_cheb(self.h, level, x.h, y.h))
+
+    def schur_solve(self, f, u, gamma, prec=SCHUR_PREC_NONE, max_it=1000, tol=1e-12, level=0):
+        """-> (iterations, final relative residual); gamma: initial guess in, solution out"""
+        its, rr = C.c_int(), C.c_double()
+        check(lib().te_schur_solve(self.h, level, int(prec), f.h, u.h, gamma.h, max_it, tol, C.byref(its), C.byref(rr)))
+        return its.value, rr.value
 
     def sync(self):
         check(lib().te_gmg_sync(self.h))

@@ -157,5 +157,19 @@ int te_hier_level_l2g(const te_hier *h, int level, int32_t *l2g)
 	copyOut(l2g, h->h.levels[level].l2g);
 	return TE_OK;
 }
+int te_hier_num_ifaces(const te_hier *h, int level, int *out)
+{
+	if (!h || !out || level < 0 || level >= (int) h->h.levels.size()) return te::fail(TE_EINVAL, "te_hier_num_ifaces: bad argument");
+	if (h->h.nranks > 1) return te::fail(TE_ESTATE, "te_hier_num_ifaces: interface tables exist on single-rank hierarchies only");
+	*out = h->h.levels[level].num_ifaces;
+	return TE_OK;
+}
+int te_hier_iface_index(const te_hier *h, int level, int32_t *out)
+{
+	if (!h || !out || level < 0 || level >= (int) h->h.levels.size()) return te::fail(TE_EINVAL, "te_hier_iface_index: bad argument");
+	if (h->h.nranks > 1) return te::fail(TE_ESTATE, "te_hier_iface_index: interface tables exist on single-rank hierarchies only");
+	copyOut(out, h->h.levels[level].iface_own);
+	return TE_OK;
+}
 void te_hier_destroy(te_hier *h) { delete h; }
 } // extern "C"

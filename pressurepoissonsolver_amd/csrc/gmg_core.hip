@@ -13,7 +13,7 @@ const char *kclassName[KC_COUNT] = {"stencil_apply", "stencil_resid", "stencil_j
 const char *optName[O_COUNT] = {"TE_2D_SIMPLE", "TE_2D_NO_MFMA", "TE_2D_NO_PF", "TE_2D_NO_MR_FUSE", "TE_2D_TPB", "TE_NO_FUSE2", "TE_NO_FUSE3",
                                 "TE_NO_FUSE3_CF", "TE_NO_CFP", "TE_NO_XF", "TE_NO_FCORR", "TE_NO_FCORR_CF", "TE_NO_GTAB", "TE_NO_OVERLAP",
                                 "TE_OVERLAP_MIN", "TE_NO_PS_FACES", "TE_PS_MODE", "TE_PS_SLOW", "TE_RBGS_NOSLAB", "TE_ZS_FORCE", "TE_NO_ZS8",
-                                "TE_RESWEEP_V", "TE_EXCHANGE_TIMEOUT", "TE_NO_VERIFY", "TE_RCCL_LOOPBACK", "TE_ZR_AHEAD", "TE_NO_BICG_FUSE", "TE_POST_EXCHANGE", "TE_REPL_BLOCKS", "TE_PACK_FACES", "TE_OVERLAP_MODE", "TE_PUSH_TIMEOUT", "TE_NO_BICG_XF", "TE_PUSH_FAULT", "TE_2D_NO_FOLD", "TE_2D_NO_SYM", "TE_PUSH_NONFATAL", "TE_PS_NO_HALF", "TE_PS_HALF_MAX", "TE_NO_GTAB2", "TE_NO_RS6_CF", "TE_NO_RS6_FIXUP", "TE_NO_CFP59"};
+                                "TE_RESWEEP_V", "TE_EXCHANGE_TIMEOUT", "TE_NO_VERIFY", "TE_RCCL_LOOPBACK", "TE_ZR_AHEAD", "TE_NO_BICG_FUSE", "TE_POST_EXCHANGE", "TE_REPL_BLOCKS", "TE_PACK_FACES", "TE_OVERLAP_MODE", "TE_PUSH_TIMEOUT", "TE_NO_BICG_XF", "TE_PUSH_FAULT", "TE_2D_NO_FOLD", "TE_2D_NO_SYM", "TE_PUSH_NONFATAL", "TE_PS_NO_HALF", "TE_PS_HALF_MAX", "TE_NO_GTAB2", "TE_NO_RS6_CF", "TE_NO_RS6_FIXUP", "TE_NO_CFP59", "TE_SCHUR_FULL"};
 
 void drainEvents(te_gmg *g)
 {
@@ -123,6 +123,10 @@ int buildLevel(te_gmg *g, const Hierarchy &H, int li)
 	L->n   = n;
 	L->P   = lv.P;
 	L->P_global = lv.P_global;
+	L->nif        = lv.num_ifaces;
+	L->if_own     = lv.iface_own;
+	L->if_start   = lv.iface_start;
+	L->if_contrib = lv.iface_contrib;
 	L->index    = li;
 	L->replicated = lv.replicated;
 	L->gathered = lv.replicated || (H.nranks > 1 && std::all_of(lv.g_rank.begin(), lv.g_rank.end(), [&](int32_t r) { return r == lv.g_rank[0]; }));
@@ -856,6 +860,7 @@ void te_gmg_destroy(te_gmg *g)
 	}
 	for (te_vec *v : g->bicg_work)
 		if (v) te_vec_destroy(v);
+	schurFree(g);
 	for (auto &e : g->ev_pool) {
 		(void) hipEventDestroy(e.a);
 		(void) hipEventDestroy(e.b);
@@ -889,6 +894,30 @@ int te_vec_create(te_gmg *g, int level, te_vec **out)
 			return te::fail(TE_EINVAL, "te_vec_create: bad argument");
 		HIPCHK(hipSetDevice(g->device));
 		return newVec(g, level, out);
+	});
+}
+
+int te_vec_create_iface(te_gmg *g, int level, te_vec **out)
+{
+	return guarded([&]() -> int {
+		if (!g || !out || level < 0 || level >= (int) g->levels.size())
+			return te::fail(TE_EINVAL, "te_vec_create_iface: bad argument");
+		LevelHost &L = *g->levels[level];
+		if (g->nranks > 1 || L.nif < 0) return te::fail(TE_ESTATE, "te_vec_create_iface: interface vectors exist on single-rank hierarchies only");
+		HIPCHK(hipSetDevice(g->device));
+		auto v   = std::make_unique<te_vec>();
+		v->g     = g;
+		v->level = level;
+		v->iface = true;
+		v->n     = (size_t) L.nif * L.nf;
+		HIPCHK(hipMalloc(&v->d, sizeof(double) * std::max<size_t>(v->n, 2)));
+		hipError_t e = hipMemsetAsync(v->d, 0, sizeof(double) * v->n, g->stream);
+		if (e != hipSuccess) {
+			(void) hipFree(v->d);
+			return te::fail(TE_EHIP, std::string("hipMemsetAsync: ") + hipGetErrorString(e));
+		}
+		*out = v.release();
+		return TE_OK;
 	});
 }
 
@@ -975,7 +1004,7 @@ int te_vec_upload_patches(te_vec *v, int first_patch, int npatches, const double
 {
 	return guarded([&]() -> int {
 		if (!v || !host) return te::fail(TE_EINVAL, "te_vec_upload_patches: null");
-		const size_t nc = v->g->levels[v->level]->nc;
+		const size_t nc = v->iface ? v->g->levels[v->level]->nf : v->g->levels[v->level]->nc; // (interface blocks)
 		if (first_patch < 0 || npatches < 0 || ((size_t) first_patch + npatches) * nc > v->n)
 			return te::fail(TE_EINVAL, "te_vec_upload_patches: patch range outside the vector");
 		if (npatches == 0) return TE_OK;
@@ -991,7 +1020,7 @@ int te_vec_download_patches(const te_vec *v, int first_patch, int npatches, doub
 {
 	return guarded([&]() -> int {
 		if (!v || !host) return te::fail(TE_EINVAL, "te_vec_download_patches: null");
-		const size_t nc = v->g->levels[v->level]->nc;
+		const size_t nc = v->iface ? v->g->levels[v->level]->nf : v->g->levels[v->level]->nc; // (interface blocks)
 		if (first_patch < 0 || npatches < 0 || ((size_t) first_patch + npatches) * nc > v->n)
 			return te::fail(TE_EINVAL, "te_vec_download_patches: patch range outside the vector");
 		if (npatches == 0) return TE_OK;

@@ -53,6 +53,7 @@ struct te_vec {
 	int     level = 0;
 	double *d     = nullptr;
 	size_t  n     = 0;
+	bool    iface = false; // an interface vector of the level (te_vec_create_iface): num_ifaces * n^(dim-1) doubles
 };
 
 namespace tei
@@ -82,7 +83,7 @@ extern const char *kclassName[KC_COUNT]; // (gmg_core.hip)
 enum Opt : int {
 	O_2D_SIMPLE, O_2D_NO_MFMA, O_2D_NO_PF, O_2D_NO_MR_FUSE, O_2D_TPB, O_NO_FUSE2, O_NO_FUSE3, O_NO_FUSE3_CF, O_NO_CFP, O_NO_XF,
 	O_NO_FCORR, O_NO_FCORR_CF, O_NO_GTAB, O_NO_OVERLAP, O_OVERLAP_MIN, O_NO_PS_FACES, O_PS_MODE, O_PS_SLOW, O_RBGS_NOSLAB,
-	O_ZS_FORCE, O_NO_ZS8, O_RESWEEP_V, O_EXCHANGE_TIMEOUT, O_NO_VERIFY, O_RCCL_LOOPBACK, O_ZR_AHEAD, O_NO_BICG_FUSE, O_POST_EXCHANGE, O_REPL_BLOCKS, O_PACK_FACES, O_OVERLAP_MODE, O_PUSH_TIMEOUT, O_NO_BICG_XF, O_PUSH_FAULT, O_2D_NO_FOLD, O_2D_NO_SYM, O_PUSH_NONFATAL, O_PS_NO_HALF, O_PS_HALF_MAX, O_NO_GTAB2, O_NO_RS6_CF, O_NO_RS6_FIXUP, O_NO_CFP59, O_COUNT
+	O_ZS_FORCE, O_NO_ZS8, O_RESWEEP_V, O_EXCHANGE_TIMEOUT, O_NO_VERIFY, O_RCCL_LOOPBACK, O_ZR_AHEAD, O_NO_BICG_FUSE, O_POST_EXCHANGE, O_REPL_BLOCKS, O_PACK_FACES, O_OVERLAP_MODE, O_PUSH_TIMEOUT, O_NO_BICG_XF, O_PUSH_FAULT, O_2D_NO_FOLD, O_2D_NO_SYM, O_PUSH_NONFATAL, O_PS_NO_HALF, O_PS_HALF_MAX, O_NO_GTAB2, O_NO_RS6_CF, O_NO_RS6_FIXUP, O_NO_CFP59, O_SCHUR_FULL, O_COUNT
 };
 extern const char *optName[O_COUNT]; // (gmg_core.hip)
 // options that shape the level tables te_gmg_create builds: fixed for the solver's lifetime
@@ -225,6 +226,9 @@ struct LevelHost {
 	int             n_pure2 = 0;
 	// scratch
 	std::unique_ptr<te_vec> u, f, r, t;
+	// interfaces (single rank; mesh.hpp Level::iface_*): host copies, uploaded by the Schur route at its first use (gmg_schur.hip)
+	int                  nif = -1;
+	std::vector<int32_t> if_own, if_start, if_contrib;
 
 	Level2D dev2() const
 	{
@@ -392,6 +396,7 @@ struct te_gmg {
 	void                                   *allreduce_user = nullptr;
 	// schedule check (te_gmg_verify_schedule): exchanges are recorded instead of performed
 	te_vec *bicg_work[8] = {nullptr}; // te_bicgstab's work vectors (level 0), allocated at its first call
+	struct SchurWs *schur = nullptr;  // the Schur route's device tables and work vectors (gmg_schur.hip), made at its first use
 	const PendingRhs *pending_rhs = nullptr; // set by te_bicgstab around a cycle: level 0's right-hand side is still to be formed
 	bool recording = false;
 	double bcgs_tol = 1e-12; // BiCGStabSolver(op, tol = 1e-12, max_it = 1000), BiCGStabSolver.h:103-108
@@ -562,7 +567,7 @@ inline int gridFor(size_t work_items, int tpb, int cap = 4096)
 	return (int) b;
 }
 
-inline bool sameShape(const te_vec *a, const te_vec *b) { return a && b && a->g == b->g && a->level == b->level; }
+inline bool sameShape(const te_vec *a, const te_vec *b) { return a && b && a->g == b->g && a->level == b->level && a->iface == b->iface; }
 
 // ---- gmg_core.hip
 int  newVec(te_gmg *g, int level, te_vec **out);
@@ -672,6 +677,9 @@ int zeroSweepResid(te_gmg *g, LevelHost &L, const double *f, double *out, double
 int launchRbgs(te_gmg *g, LevelHost &L, const double *u, const double *f, double *out, bool zero_guess = false,
                const double *prolong_from = nullptr, const double *xf_in = nullptr, double *xf_out = nullptr);
 int residRestrict(te_gmg *g, LevelHost &L, const double *u, const double *f, double *coarse, const double *xf_in = nullptr);
+bool psOnePass(const te_gmg *g, const LevelHost &L);  // (gmg_patchsolve.hip) the single-pass patch-solve kernels on this level
+int  psSymCount(const te_gmg *g, const LevelHost &L); // ... of them, patches that take k_ps_sym
+bool psAllSym32(const te_gmg *g, const LevelHost &L); // 32^3 patches, every one through the single-pass k_ps_sym
 int patchSolve(te_gmg *g, LevelHost &L, const double *f, double *u, bool zero_guess = false, const double *prolong_from = nullptr,
                bool *swapped = nullptr);
 int doRestrict(te_gmg *g, int fine_level, const double *fine, double *coarse);
@@ -696,6 +704,8 @@ int prolong2d(te_gmg *g, LevelHost &L, const double *coarse, double *fine);
 int zeroSweepResid2d(te_gmg *g, LevelHost &L, const double *f, double *out, double *coarse, bool store_u, const Fold2DHost *fold_in = nullptr,
                      bool skip_fixup = false);
 int resweepProlong2d(te_gmg *g, LevelHost &L, const double *f, double *out, const double *prolong_from);
+// ---- gmg_schur.hip
+void schurFree(te_gmg *g); // (te_gmg_destroy)
 // ---- gmg_cycle.hip
 int visit(te_gmg *g, const te_cycle_opts *o, int l, const te_vec *f, te_vec *u, bool u_zero);
 int vcycleWith(te_gmg *g, const te_cycle_opts *o, const te_vec *f, te_vec *u, const PendingRhs *pending); // te_vcycle; `pending`: see PendingRhs
@@ -783,5 +793,6 @@ static inline int checkLevelVec(te_gmg *g, int level, const te_vec *v, const cha
 {
 	if (!g || !v || level < 0 || level >= (int) g->levels.size() || v->g != g || v->level != level)
 		return te::fail(TE_EINVAL, std::string(who) + ": vector does not belong to this level");
+	if (v->iface) return te::fail(TE_EINVAL, std::string(who) + ": an interface vector where a domain vector is needed");
 	return TE_OK;
 }

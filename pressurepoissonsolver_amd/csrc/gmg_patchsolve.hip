@@ -4,6 +4,24 @@
 
 namespace tei
 {
+// How a level's 32^3 patch solve is routed (patchSolveN below; the Schur route's faces-only T relies on the same decision,
+// gmg_schur.hip): the single-pass kernels -- by the GLOBAL patch count, TE_PS_MODE pins it --, and among them how many patches
+// take k_ps_sym (pure axes; none under 1pass-dense).
+bool psOnePass(const te_gmg *g, const LevelHost &L)
+{
+	const char *mode = g->cfg.str(O_PS_MODE);
+	return mode ? !strncmp(mode, "1pass", 5) : L.P_global >= 256;
+}
+int psSymCount(const te_gmg *g, const LevelHost &L)
+{
+	const char *mode = g->cfg.str(O_PS_MODE);
+	return (mode && !strcmp(mode, "1pass-dense")) ? 0 : (L.sym_ok ? L.P : L.n_pure);
+}
+bool psAllSym32(const te_gmg *g, const LevelHost &L)
+{
+	return L.dim == 3 && L.n == 32 && L.P > 0 && !g->cfg.has(O_PS_SLOW) && psOnePass(g, L) && psSymCount(g, L) == L.P;
+}
+
 template <int N> int patchSolveN(te_gmg *g, LevelHost &L, const double *f, double *u, double *s0, double *s1,
                                  bool zero_guess, const double *prolong_from)
 {
@@ -21,7 +39,7 @@ template <int N> int patchSolveN(te_gmg *g, LevelHost &L, const double *f, doubl
 		const char *mode     = g->cfg.str(O_PS_MODE);
 		// (the GLOBAL patch count decides: k_ps_sym and the three-pass kernels differ in the last bits, and a sharded run must
 		// take the arithmetic path of the single-rank run -- 512^3 on 8 ranks has 64 local patches of 512 on level 1)
-		const bool  one_pass = mode ? !strncmp(mode, "1pass", 5) : L.P_global >= 256;
+		const bool  one_pass = psOnePass(g, L);
 		const int   seg      = (one_pass || mode) ? 1 : (L.P >= 128 ? 2 : (L.P >= 64 ? 4 : 8));
 		const dim3 gp(L.P, seg), b256(256);
 		// x-face columns of the old iterate, if its producer exported them (te_vcycle only: see xfFor)
@@ -88,15 +106,13 @@ template <int N> int patchSolveN(te_gmg *g, LevelHost &L, const double *f, doubl
 				lds_ok = true;
 			}
 			// (decided here as well as below: the class of the launch is part of its timing scope)
-			const bool dense_only0 = mode && !strcmp(mode, "1pass-dense");
-			const bool faces0 = faces_req && L.f6buf.p && !dense_only0 && (L.sym_ok ? L.P : L.n_pure) == L.P;
+			const bool faces0 = faces_req && L.f6buf.p && psSymCount(g, L) == L.P;
 			Timed         t(g, faces0 ? KC_PS_MFMA_FACES : KC_PS_MFMA, total, true);
 			const dim3    b512(512);
 			const double *cp = zero_guess ? (const double *) nullptr : (const double *) L.corr.p;
 			// pure axes: half-size transforms, one resident workgroup per CU walks over the patches (k_ps_sym);
 			// patches with a mixed Dirichlet/Neumann axis: full transforms, one workgroup per patch (k_ps_fused)
-			const bool dense_only = mode && !strcmp(mode, "1pass-dense");
-			const int  n_sym = dense_only ? 0 : (L.sym_ok ? L.P : L.n_pure), n_mix = L.P - n_sym;
+			const int  n_sym = psSymCount(g, L), n_mix = L.P - n_sym;
 			const int32_t *lst_sym = (n_sym > 0 && n_mix > 0) ? L.ps_list.p : nullptr;
 			const int32_t *lst_mix = (n_sym > 0 && n_mix > 0) ? L.ps_list.p + n_sym : nullptr;
 			if (n_sym > 0) {

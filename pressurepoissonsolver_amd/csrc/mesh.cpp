@@ -356,6 +356,60 @@ Hierarchy Hierarchy::build(const Tree &t, int n, bool neumann, int max_levels,
 			lv.P = (int) lv.l2g.size();
 		}
 	}
+	if (nranks == 1)
+		for (auto &lv : h.levels) buildIfaces(lv);
 	return h;
+}
+
+void buildIfaces(Level &lv)
+{
+	const int NS = 2 * lv.dim, P = lv.P_global, NQ = 1 << (lv.dim - 1);
+	std::map<int64_t, int> rev; // interface id -> local index, first seen first
+	auto get = [&](int64_t id) {
+		auto it = rev.find(id);
+		if (it != rev.end()) return it->second;
+		const int v = (int) rev.size();
+		rev[id]     = v;
+		return v;
+	};
+	struct C {
+		int iface, p, s, kind, q;
+	};
+	std::vector<C> cs;
+	lv.iface_own.assign((size_t) P * NS, -1);
+	for (int p = 0; p < P; p++) {
+		for (int s = 0; s < NS; s++) {
+			const size_t f = (size_t) p * NS + s;
+			const int    kind = lv.g_nbr_kind[f];
+			const int64_t mine = (int64_t) lv.g_id[p] * NS + s;
+			if (kind == NBR_NORMAL) { // the id belongs to the lower side's patch (SchurInfo.h:141-150)
+				const int own = get((s & 1) ? (int64_t) lv.g_id[lv.g_nbr[f * 4]] * NS + (s ^ 1) : mine);
+				lv.iface_own[f] = own;
+				cs.push_back({own, p, s, IF_NORMAL, 0});
+			} else if (kind == NBR_COARSE) {
+				const int own = get(mine);
+				const int oth = get((int64_t) lv.g_id[lv.g_nbr[f * 4]] * NS + (s ^ 1));
+				lv.iface_own[f] = own;
+				cs.push_back({own, p, s, IF_FINE_TO_FINE, lv.g_nbr_orth[f]});
+				cs.push_back({oth, p, s, IF_FINE_TO_COARSE, lv.g_nbr_orth[f]});
+			} else if (kind == NBR_FINE) {
+				const int own = get(mine);
+				lv.iface_own[f] = own;
+				cs.push_back({own, p, s, IF_COARSE_TO_COARSE, 0});
+				for (int q = 0; q < NQ; q++) cs.push_back({get((int64_t) lv.g_id[lv.g_nbr[f * 4 + q]] * NS + (s ^ 1)), p, s, IF_COARSE_TO_FINE, q});
+			}
+		}
+	}
+	lv.num_ifaces = (int) rev.size();
+	// bucket by interface; inside a bucket the (patch, side) order of the walk above stays (the order the oracle sums in)
+	std::stable_sort(cs.begin(), cs.end(), [](const C &a, const C &b) { return a.iface < b.iface; });
+	lv.iface_start.assign(lv.num_ifaces + 1, 0);
+	lv.iface_contrib.clear();
+	lv.iface_contrib.reserve(cs.size() * 4);
+	for (const C &c : cs) {
+		lv.iface_start[c.iface + 1]++;
+		lv.iface_contrib.insert(lv.iface_contrib.end(), {c.p, c.s, c.kind, c.q});
+	}
+	for (int i = 0; i < lv.num_ifaces; i++) lv.iface_start[i + 1] += lv.iface_start[i];
 }
 } // namespace te

@@ -85,6 +85,26 @@ struct Level {
 	/// every rank holds (and computes) the whole level: g_rank is this rank's number for every patch, P == P_global
 	bool                 replicated = false;
 	std::vector<int32_t> l2g;     ///< [P] local -> global index
+
+	// ---- interfaces (single-rank hierarchies only; num_ifaces = -1 on a sharded one) --------------------------------
+	/// The interface unknowns of the Schur-complement route: one block of n^(dim-1) values per interface, numbered in
+	/// first-seen order over the patches and their sides as SchurHelper<D>::indexDomainIfacesLocal does (SchurHelper.h:
+	/// 377-397; ids SchurInfo.h:141-150 normal, :229-237 coarse, :322-331 fine).
+	int                  num_ifaces = -1;
+	std::vector<int32_t> iface_own;   ///< [P][2*dim] the interface patch p sees on side s, -1 on a physical face
+	/// what interpolateToInterface (SchurHelper.h:333-343) sums into each interface: the contributions of interface i are
+	/// iface_contrib[iface_start[i] .. iface_start[i+1]), each (patch, side, IfaceKind, quadrant), in (patch, side) order
+	std::vector<int32_t> iface_start;   ///< [num_ifaces + 1]
+	std::vector<int32_t> iface_contrib; ///< [..][4]
+};
+
+/// the five IfaceType cases of TriLinInterp / BilinearInterpolator, seen from the contributing patch's side
+enum IfaceKind : int32_t {
+	IF_NORMAL = 0,          ///< same-level neighbour: 1/2 of the own face layer
+	IF_FINE_TO_FINE = 1,    ///< this patch is the fine side, its own interface
+	IF_FINE_TO_COARSE = 2,  ///< this patch is the fine side, the coarse neighbour's interface (quadrant = its position there)
+	IF_COARSE_TO_COARSE = 3,///< this patch is the coarse side, its own interface
+	IF_COARSE_TO_FINE = 4   ///< this patch is the coarse side, fine neighbour `quadrant`'s interface
 };
 
 /// Where the levels with few patches live when nranks > 1 (the patches_per_proc idea of CycleFactory3d.cpp:104 without
@@ -114,6 +134,9 @@ struct Hierarchy {
 	static Hierarchy build(const Tree &t, int n, bool neumann, int max_levels,
 	                       double patches_per_proc, int rank, int nranks, const Placement &pl = Placement());
 };
+
+/// fills the interface tables of `lv` (all patches of the level, global order)
+void buildIfaces(Level &lv);
 
 uint64_t mortonKey(const double *starts, const double *root_starts, const double *root_lengths,
                    int dim, int bits);

@@ -98,7 +98,9 @@ struct PssPlane {
 // they replace ran on the vector ALU -- which on gfx950 is the unit the fp64 matrix instruction executes on (tools/mfma_valu.hip:
 // v_fma_f64 issued by one wave of a SIMD and v_mfma_f64 issued by the other take the SUM of their times): 64 divisions of ~ 11
 // instructions per lane and patch were a sixth of the kernel's pipe time.
-template <bool CORR, bool FACES = false>
+// NOF (the Schur route's T gamma = Interp(Solve(0, gamma)), gmg_schur.hip): the right-hand side is zero and never read -- the planes
+// start as zeros minus their interface terms; with FACES the kernel reads 1.5 B per site (corr) and writes 1.5.
+template <bool CORR, bool FACES = false, bool NOF = false>
 __global__ __launch_bounds__(512) void k_ps_sym(int P, const int32_t *__restrict__ plan, const double *__restrict__ frag,
                                                 const double *__restrict__ inv, const int32_t *__restrict__ itab,
                                                 const double *__restrict__ in,
@@ -143,6 +145,15 @@ __global__ __launch_bounds__(512) void k_ps_sym(int P, const int32_t *__restrict
 #endif
 		}
 	};
+	auto loadIn = [&](const Lane &q, PssPlane &d, const double *base) { // a plane of the right-hand side (NOF: zeros, nothing read)
+		if constexpr (NOF) {
+			(void) q, (void) base;
+#pragma unroll
+			for (int k = 0; k < 4; k++) d.ll[k] = d.lh[k] = d.hl[k] = d.hh[k] = 0.0;
+		} else {
+			loadPlane(q, d, base);
+		}
+	};
 	// ring terms of plane z: lane l < 32 holds W[l] and S[l], l >= 32 holds E[l-32] and N[l-32]
 	auto loadRing = [&](const Lane &q, double(&c)[2], const double *cr, int z) {
 		c[0] = cr[(q.l >> 5) * NN + N * z + (q.l & 31)];
@@ -176,8 +187,8 @@ __global__ __launch_bounds__(512) void k_ps_sym(int P, const int32_t *__restrict
 	if (it < P) {
 		const Lane q   = lane();
 		const int  pid = patchAt(it);
-		loadPlane(q, s0, in + ((size_t) pid * N + zof(0)) * NN);
-		loadPlane(q, s1, in + ((size_t) pid * N + zof(1)) * NN);
+		loadIn(q, s0, in + ((size_t) pid * N + zof(0)) * NN);
+		loadIn(q, s1, in + ((size_t) pid * N + zof(1)) * NN);
 		if (CORR) loadRing(q, c, corr + (size_t) pid * 6 * NN, zof(0));
 	}
 	// A CU keeps about one L1's worth (32 KiB) of loads in flight, so a burst of plane requests takes several
@@ -188,10 +199,10 @@ __global__ __launch_bounds__(512) void k_ps_sym(int P, const int32_t *__restrict
 		const int  np = patchAt(it + gridDim.x);
 		const Lane qn = lane();
 		if (which == 0) {
-			loadPlane(qn, s0, in + ((size_t) np * N + zof(0)) * NN);
+			loadIn(qn, s0, in + ((size_t) np * N + zof(0)) * NN);
 			if (CORR) loadRing(qn, c, corr + (size_t) np * 6 * NN, zof(0));
 		} else {
-			loadPlane(qn, s1, in + ((size_t) np * N + zof(1)) * NN);
+			loadIn(qn, s1, in + ((size_t) np * N + zof(1)) * NN);
 		}
 	};
 
@@ -276,7 +287,7 @@ __global__ __launch_bounds__(512) void k_ps_sym(int P, const int32_t *__restrict
 				applyRing(q, s0, c);
 			}
 			yfwd(s0);
-			loadPlane(q, s0, ip + zof(2) * NN);
+			loadIn(q, s0, ip + zof(2) * NN);
 			xfwd(zof(0), hi[0]);
 			PSS_FENCE(0);
 			// plane z_1 (slot 1), then request z_3 -> slot 1
@@ -285,7 +296,7 @@ __global__ __launch_bounds__(512) void k_ps_sym(int P, const int32_t *__restrict
 				applyRing(q, s1, cn);
 			}
 			yfwd(s1);
-			loadPlane(q, s1, ip + zof(3) * NN);
+			loadIn(q, s1, ip + zof(3) * NN);
 			xfwd(zof(1), hi[1]);
 			PSS_FENCE(1);
 			// plane z_2 (slot 0), then the z-face term of z_3 -> slot 0

@@ -10,6 +10,12 @@
 //   HipRestrictor<D>   : GMG::Restrictor<D>   (GMG/Restrictor.h:39-40)       == AvgRstr
 //   HipInterpolator<D> : GMG::Interpolator<D> (GMG/Interpolator.h:39-40)     == DrctIntp
 //   HipCycle<D>        : Operator<D>          whole GMG::Cycle<D>::apply (GMG/Cycle.h:116-126) in one call
+// The Schur-complement route (--schur, apps/3d/steady.cpp:336-420, apps/2d/steady.cpp:383-480; single rank):
+//   HipSchurVG<D>      : VectorGenerator<D-1> SchurHelper<D>::getNewSchurVec (SchurHelper.h:156-160): HipVector<D-1> over
+//                                             an interface vector, one "patch" per interface block of n^(D-1) values
+//   HipSchurOp<D>      : Operator<D-1>        y = x - T x, the Schur operator (Operators/SchurWrapOp.h with its identity
+//                                             term); rhs() = g = Interp(Solve(f, 0)), solution() = u = Solve(f, gamma)
+//   HipChebPrec<D>     : Operator<D-1>        PolyChebPrec::apply (PolyChebPrec.cpp)
 //
 // Error convention: the reference throws `int` (`throw 3;`, e.g. GMG/InterLevelComm.h:175,
 // SchurHelper.h:129); a non-zero te_* status is rethrown the same way.
@@ -107,9 +113,11 @@ template <size_t D> class HipVector : public Vector<D>
 	te_vec                    *v = nullptr;
 	int                        level;
 	std::shared_ptr<HipMirror> mirror;
-	HipVector(std::shared_ptr<Context> ctx_, int level_) : ctx(ctx_), level(level_)
+	/// iface: an interface vector of a (D+1)-dimensional level (te_vec_create_iface): its "patches" are the interface blocks,
+	/// n^D values each, in SchurHelper's local order
+	HipVector(std::shared_ptr<Context> ctx_, int level_, bool iface = false) : ctx(ctx_), level(level_)
 	{
-		check(te_vec_create(ctx->g, level, &v));
+		check(iface ? te_vec_create_iface(ctx->g, level, &v) : te_vec_create(ctx->g, level, &v));
 		size_t cells = 1;
 		for (size_t i = 0; i < D; i++) cells *= ctx->n;
 		this->num_local_patches = (int) (te_vec_size(v) / cells);
@@ -267,6 +275,62 @@ template <size_t D> class HipCycle : public Operator<D>
 	void apply(std::shared_ptr<const Vector<D>> f, std::shared_ptr<Vector<D>> u) const override
 	{
 		check(te_vcycle(ctx->g, &opts, HipVector<D>::raw(f), const_cast<te_vec *>(HipVector<D>::raw(u))));
+	}
+};
+// ------------------------------------------------------------------------- Schur-complement route (single rank)
+template <size_t D> class HipSchurVG : public VectorGenerator<D - 1>
+{
+	std::shared_ptr<Context> ctx;
+	int                      level;
+
+	public:
+	HipSchurVG(std::shared_ptr<Context> ctx_, int level_ = 0) : ctx(ctx_), level(level_) {}
+	std::shared_ptr<Vector<D - 1>> getNewVector() override
+	{
+		return std::shared_ptr<Vector<D - 1>>(new HipVector<D - 1>(ctx, level, true));
+	}
+};
+
+/// The Schur system S gamma = g of the reference's --schur drivers, solved by the reference's own BiCGStab<D-1>:
+///   auto vg = make_shared<HipSchurVG<3>>(ctx); auto S = make_shared<HipSchurOp<3>>(ctx);
+///   auto gamma = vg->getNewVector(), g = vg->getNewVector(); S->rhs(f, g);
+///   BiCGStab<2>::solve(vg, S, gamma, g, make_shared<HipChebPrec<3>>(ctx)); S->solution(f, gamma, u);
+template <size_t D> class HipSchurOp : public Operator<D - 1>
+{
+	std::shared_ptr<Context> ctx;
+	int                      level;
+
+	public:
+	HipSchurOp(std::shared_ptr<Context> ctx_, int level_ = 0) : ctx(ctx_), level(level_) {}
+	void apply(std::shared_ptr<const Vector<D - 1>> x, std::shared_ptr<Vector<D - 1>> b) const override
+	{
+		check(te_schur_apply(ctx->g, level, HipVector<D - 1>::raw(x), const_cast<te_vec *>(HipVector<D - 1>::raw(b))));
+	}
+	/// g = Interp(Solve(f, 0)): the right-hand side (solveWithInterface's diff at gamma = 0, SchurHelper.h:280-297)
+	void rhs(std::shared_ptr<const Vector<D>> f, std::shared_ptr<Vector<D - 1>> g) const
+	{
+		HipVector<D>     u(ctx, level);
+		HipVector<D - 1> zero(ctx, level, true);
+		check(te_solve_with_interface(ctx->g, level, HipVector<D>::raw(f), u.v, zero.v, const_cast<te_vec *>(HipVector<D - 1>::raw(g))));
+	}
+	/// u = Solve(f, gamma): the domain solution once gamma solves the Schur system
+	void solution(std::shared_ptr<const Vector<D>> f, std::shared_ptr<const Vector<D - 1>> gamma, std::shared_ptr<Vector<D>> u) const
+	{
+		check(te_solve_with_interface(ctx->g, level, HipVector<D>::raw(f), const_cast<te_vec *>(HipVector<D>::raw(u)),
+		                              HipVector<D - 1>::raw(gamma), nullptr));
+	}
+};
+
+template <size_t D> class HipChebPrec : public Operator<D - 1>
+{
+	std::shared_ptr<Context> ctx;
+	int                      level;
+
+	public:
+	HipChebPrec(std::shared_ptr<Context> ctx_, int level_ = 0) : ctx(ctx_), level(level_) {}
+	void apply(std::shared_ptr<const Vector<D - 1>> x, std::shared_ptr<Vector<D - 1>> b) const override
+	{
+		check(te_schur_cheb(ctx->g, level, HipVector<D - 1>::raw(x), const_cast<te_vec *>(HipVector<D - 1>::raw(b))));
 	}
 };
 } // namespace tehip
