@@ -1,7 +1,8 @@
 // What the translation units of the device half of include/te_hip.h share: the solver's state (te_gmg, one LevelHost per level),
 // the option table, the timing scopes, and the functions one unit calls in another. Host C++ + HIP for gfx950 only; there is
 // no CPU fallback anywhere: if HIP cannot give us a device, te_gmg_create fails with TE_EHIP.
-//   gmg_core.hip       level tables on the device (buildLevel), solver / vector life cycle, options, profiling, Init kernels
+//   level_tables.cpp   what the tables of a level hold (computeLevelTables): host C++ only, no device header
+//   gmg_core.hip       places them on the device (buildLevel), solver / vector life cycle, options, profiling, Init kernels
 //   gmg_transport.hip  exchanges between ranks: RCCL binding, host callback, direct-store transport, scalar reductions, watchdog
 //   gmg_launch3d.hip   every 3D kernel launch (stencil, sweeps, fused sweeps, patch solves, transfers)
 //   gmg_launch2d.hip   the 2D twins
@@ -9,6 +10,7 @@
 //   gmg_krylov.hip     Vector<D> BLAS-1 entries and te_bicgstab (BiCGStab.h:45-106)
 #pragma once
 #include "capi_common.hpp"
+#include "level_tables.hpp"
 #include <hip/hip_ext.h>
 #include <rccl/rccl.h> // enum values and ncclUniqueId only: the library itself is dlopen'ed (te_gmg_use_rccl)
 #include "kernels3d.hpp"
@@ -144,13 +146,6 @@ template <typename T> struct DevBuf {
 		if (!h.empty()) HIPCHK(hipMemcpy(p, h.data(), sizeof(T) * h.size(), hipMemcpyHostToDevice));
 		return TE_OK;
 	}
-};
-
-// one exchange = for every peer: send [send_off, +send_cnt) and receive [recv_off, +recv_cnt) doubles
-struct ExPlan {
-	std::vector<int32_t> peers;
-	std::vector<int64_t> send_off, send_cnt, recv_off, recv_cnt;
-	bool empty() const { return peers.empty(); }
 };
 
 struct LevelHost;

@@ -1444,14 +1444,13 @@ __global__ __launch_bounds__(256) void k_patch_solve2d_mfma(Level2D L, const int
 // Each of the four stages is 32 instead of 64 v_mfma_f64_16x16x4 per wave (the kernel is bound by them: 54 of 78.6 TFLOP/s on the
 // full-size products); the butterflies ride on the LDS reads and on the accumulators. Transformed data sits in parity-split order
 // (position c < 32: wave number 2c, c >= 32: 2(c - 32) + 1) between the stages, along both axes.
-// sym [plan][stage 4][k-step 8][t 4][lane 64]: the matrix fragments in MFMA operand order (built by the host, gmg_core.hip):
+// sym [plan][stage 4][k-step 8][t 4][lane 64]: the matrix fragments in MFMA operand order (built by the host, level_tables.cpp; PS2S_STAGE and PS2S_PLAN: table_layout.hpp):
 //   stage 0 (B side): t = column tile;            F_x[kx(t, j)][4 ks + g]
 //   stage 1 (A side): t = wave;                   F_y[ky(w, j)][4 ks + g]
 //   stage 2 (B side): t = parity * 2 + column tile of x' < 32;   G_x[16 ct + j][2 (4 ks + g) + parity]
 //   stage 3 (A side): t = parity * 2 + row tile of y' < 32;      G_y[16 rt + j][2 (4 ks + g) + parity]
 // Only patches whose plan has two pure axes (list, n of them); the others take k_patch_solve2d_mfma. Sums run in another order
 // than there: equal to rounding (<= 1e-13).
-constexpr int PS2S_STAGE = 8 * 4 * 64, PS2S_PLAN = 4 * PS2S_STAGE;
 template <bool ZERO, bool PF, bool PROLONG = false>
 __global__ __launch_bounds__(256, PF ? 2 : 4) void k_patch_solve2d_sym(Level2D L, const int32_t *__restrict__ plan, const double *__restrict__ sym,
                                                            const double *__restrict__ inv, const int32_t *__restrict__ itab,

@@ -15,11 +15,11 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "table_layout.hpp" // FaceKind
 #include "pushkernels.hpp" // PushFlag / pushRaise: the pack kernels raise the peers' flags themselves (PackPush)
 
 namespace te
 {
-enum FaceKind : int32_t { FACE_DIRICHLET = 0, FACE_NEUMANN = 1, FACE_LOCAL = 2, FACE_GHOST = 3 };
 enum StencilMode : int { MODE_APPLY = 0, MODE_RESID = 1, MODE_JACOBI = 2, MODE_RESID_RESTRICT = 3 };
 
 // where the fused residual+restriction kernel puts the coarse right-hand side of a patch:
@@ -96,7 +96,7 @@ struct LevelDev {
 	double       *f6_out;
 	// where face layer (p, s) sits inside f6 / f6_out, in units of N*N doubles (null: at p * 6 + s). A level cut by rank
 	// boundaries keeps the layers that travel to other ranks first, in send order: the exchange sends them from where
-	// they are and no pack kernel runs (gmg_core.hip buildLevel)
+	// they are and no pack kernel runs (level_tables.cpp exchangePlan)
 	const int32_t *f6off;
 	// ghost terms that still belong to this level's right-hand side (march3d.hpp FCorrSrc), or null
 	const double *fcorr;

@@ -78,14 +78,8 @@ __global__ __launch_bounds__(256) void k_face_corr3d(LevelDev L, const double *_
 //   matrices 0, 3 (x):       B operand  bx[nb = e >> 3][ks = e & 7]               = M[(2j + nb) * 32 + 4 ks + g]
 //   matrices 1, 4, 5 (y, z): A operand  ay[mo = e >> 3][mb = (e >> 2) & 1][r = e & 3] = M[(16 mo + j) * 32 + 16 mb + g + 4 r]
 //   matrix 2 (z forward):    A operand  af[mb = e >> 3][ks = e & 7]               = M[(16 mb + j) * 32 + 4 ks + g]
-// (matFragIndex below is what gmg_core.hip fills the table with.) The values and the order of the products are unchanged.
-__host__ __device__ inline int matFragSource(int m, int lane, int e)
-{
-	const int j = lane & 15, g = lane >> 4;
-	if (m == 0 || m == 3) return (2 * j + (e >> 3)) * 32 + 4 * (e & 7) + g;
-	if (m == 2) return (16 * (e >> 3) + j) * 32 + 4 * (e & 7) + g;
-	return (16 * (e >> 3) + j) * 32 + 16 * ((e >> 2) & 1) + g + 4 * (e & 3);
-}
+// (matFragSource in table_layout.hpp is what level_tables.cpp fills the table with.) The values and the order of the products are
+// unchanged.
 // a lane's 16 values of matrix m of plan pl
 __device__ __forceinline__ void loadMatFrag(const double *__restrict__ mfrag, int pl, int m, int lane, double (&v)[16])
 {

@@ -52,12 +52,12 @@ namespace te
 //   0 y fwd  B[k = n = 4q+g][col j]  = Fy[2j+p][4q+g]        3 x inv  B[k = m = 4q+g][col j] = Gx[j][2(4q+g)+p]
 //   1 x fwd  A[i = j][k = n = g+4q]  = Fx[2j+p][g+4q]        4 y inv  A[i = j][k = m = g+4q] = Gy[j][2(g+4q)+p]
 //   2 z fwd  A[i = j][k = n = 4q+g]  = Fz[2j+p][4q+g]        5 z inv  A[i = j][k = m = g+4q] = Gz[j][2(g+4q)+p]
-constexpr int PSS_FRAG      = 6 * 2 * 4 * 64;
+// (PSS_FRAG = 6 * 2 * 4 * 64 doubles: table_layout.hpp)
 constexpr int PSS_SLAB      = 32 * 32;                             // image: [kx/2 16][z 32][ky 32] doubles
 constexpr int PSS_RING      = 16 * PSS_SLAB;                       // per-wave ring strips: [wave 8][128]
 constexpr int PSS_TAB       = PSS_RING + 8 * 128;                  // the current plan's fragment table
 constexpr int PSS_LDS_BYTES = (PSS_TAB + PSS_FRAG) * 8;            // 163840: all of a CU's LDS
-constexpr int PSS_INV       = 32 * 32 * 32;                        // one table of reciprocal eigenvalue sums
+// (PSS_INV = 32^3: one table of reciprocal eigenvalue sums, table_layout.hpp)
 #ifdef PSF_TIMING
 static __device__ long long pss_stamp[8][12];
 #define PSS_STAMP(k) do { if (blockIdx.x == 100 && l == 0 && it == (int) (blockIdx.x + 8 * gridDim.x)) pss_stamp[wave][k] = clock64(); } while (0)
