@@ -65,6 +65,26 @@ int te_hier_build(const te_mesh *m, int n, int neumann, int max_levels, double p
  * pass the same values: te_vcycle / te_bicgstab compare them across the ranks before the first cycle (TE_ESTATE, by name). */
 int te_hier_build_placed(const te_mesh *m, int n, int neumann, int max_levels, double patches_per_proc,
                          int rank, int nranks, double agglomerate, int agglomerate_max, int replicate, te_hier **out);
+/* te_hier_build_placed with one boundary kind per SIDE OF THE DOMAIN: bit s of `neumann_sides` set = side s is a Neumann boundary,
+ * clear = Dirichlet; s = 2 * axis + upper (west, east, south, north, bottom, top: Side.h:51-56, the numbering of face tables
+ * everywhere here). The reference's drivers have one --neumann flag for all sides (apps/3d/steady.cpp:318-334) although its
+ * patch operator takes one flag per side (PatchInfo.h neumann bitset, StarPatchOp.h:39-65): this is the call for walls and inflow
+ * (Neumann) next to an outflow or a free surface (Dirichlet). `neumann` != 0 of the two calls above = every bit set.
+ * TE_EINVAL for a bit at or above 2 * dim. Every rank must pass the same mask (compared with the placement, TE_ESTATE by name).
+ * One kind per side of the domain, not per patch face; no Robin conditions. */
+int te_hier_build_bc(const te_mesh *m, int n, int neumann_sides, int max_levels, double patches_per_proc,
+                     int rank, int nranks, double agglomerate, int agglomerate_max, int replicate, te_hier **out);
+/* the mask ((1 << 2 dim) - 1 for a hierarchy built with neumann = 1, 0 with neumann = 0) */
+int te_hier_neumann_sides(const te_hier *h);
+/* 1: every side is Neumann -- the operator has the constant null space, and the driver subtracts the mean of f with te_integrate /
+ * te_volume (apps/3d/steady.cpp:330-334); 0: the system is regular, no mean subtraction. */
+int te_hier_singular(const te_hier *h);
+/* The physical faces (no neighbour) of this rank's patches of a level, numbered in (patch, side) order: the blocks of a boundary
+ * vector (te_vec_create_boundary). bface_index[P_local][2*dim] = the face's number, -1 on a face with a neighbour. Sharded
+ * hierarchies number their local faces; on a level that lives on every rank, every rank numbers the whole level. Replaces nothing
+ * in the reference (Init.cpp walks PatchInfo::hasNbr per patch). */
+int te_hier_num_bfaces(const te_hier *h, int level, int *num_bfaces);
+int te_hier_bface_index(const te_hier *h, int level, int32_t *bface_index);
 /* the placement this hierarchy was built with (any pointer may be NULL) */
 int te_hier_placement(const te_hier *h, double *agglomerate, int *agglomerate_max, int *replicate);
 int te_hier_num_levels(const te_hier *h);
@@ -144,6 +164,13 @@ int    te_vec_create(te_gmg *g, int level, te_vec **out);
  * te_vec_download_patches count interface blocks instead of patches); the domain operators (te_apply, te_smooth, te_vcycle,
  * te_bicgstab, ...) refuse it with TE_EINVAL. Single rank: TE_ESTATE on a sharded hierarchy. */
 int    te_vec_create_iface(te_gmg *g, int level, te_vec **out);
+/* A boundary vector of `level`: te_hier_num_bfaces * n^(dim-1) doubles, one block per physical face of this rank's patches in
+ * te_hier_bface_index order, a block laid out like an interface block (the face's remaining axes, x fastest), zero-filled. The
+ * boundary values g (Dirichlet faces) or the derivative along the face's axis g_n (Neumann faces) of a driver whose boundary
+ * data is not one of the canned problems' or changes every time step. Every te_vec_* call takes it (te_vec_upload_patches /
+ * te_vec_download_patches count blocks); the domain operators refuse it with TE_EINVAL. Exists on sharded hierarchies too.
+ * Replaces nothing in the reference (its boundary data are std::function callbacks evaluated inside Init.cpp's loops). */
+int    te_vec_create_boundary(te_gmg *g, int level, te_vec **out);
 void   te_vec_destroy(te_vec *v);
 size_t te_vec_size(const te_vec *v);                 /* doubles (local patches * n^dim) */
 int    te_vec_upload(te_vec *v, const double *host); /* Vector<D>::getLocalData write path */
@@ -349,6 +376,20 @@ int te_volume(te_gmg *g, int level, double *out);
 #define TE_PROBLEM_GAUSS 1
 #define TE_PROBLEM_RANDOM 2
 int te_init_problem(te_gmg *g, int level, int problem, int neumann, te_vec *f, te_vec *exact);
+
+/* The boundary half of Init::initDirichlet / Init::initNeumann (apps/shared/Init.cpp:186-240, :89-146) with the data taken from a
+ * boundary vector, in place, on the device: on a Dirichlet face f -= 2 g / h^2, on a Neumann face f += g_n / h (lower side) or
+ * f -= g_n / h (upper side), g_n the derivative ALONG THE AXIS (Init.cpp's nfunx / nfuny / nfunz, not the outward normal), h the
+ * patch's spacing on that axis. Cells on edges and corners receive one term per physical side, in side order. Touches the face
+ * layers of boundary patches only; deterministic (no atomics). */
+int te_add_boundary_rhs(te_gmg *g, int level, const te_vec *bdata, te_vec *f);
+/* the canned problems' boundary data (TE_PROBLEM_TRIG / TE_PROBLEM_GAUSS): the exact solution at the face points of Dirichlet faces,
+ * its derivative along the axis on Neumann faces -- what te_init_problem_sides folds in */
+int te_boundary_sample(te_gmg *g, int level, int problem, te_vec *bdata);
+/* te_init_problem with the kind of every physical face taken from the hierarchy's side mask (te_hier_build_bc) instead of one flag:
+ * Init::initDirichlet's term on Dirichlet faces and Init::initNeumann's on Neumann faces in one pass (for mask 0 / all bits the
+ * very bits of te_init_problem with neumann = 0 / 1). */
+int te_init_problem_sides(te_gmg *g, int level, int problem, te_vec *f, te_vec *exact);
 
 /* kernel timing hooks for bench.py: HIP-event time of the last te_vcycle's dominant kernel */
 int te_gmg_profile(te_gmg *g, int enable);

@@ -65,6 +65,11 @@ SYMBOLS = {
     "te_mesh_destroy": (None, [_P]),
     "te_hier_build": (_I, [_P, _I, _I, _I, _D, _I, _I, C.POINTER(_P)]),
     "te_hier_build_placed": (_I, [_P, _I, _I, _I, _D, _I, _I, _D, _I, _I, C.POINTER(_P)]),
+    "te_hier_build_bc": (_I, [_P, _I, _I, _I, _D, _I, _I, _D, _I, _I, C.POINTER(_P)]),
+    "te_hier_neumann_sides": (_I, [_P]),
+    "te_hier_singular": (_I, [_P]),
+    "te_hier_num_bfaces": (_I, [_P, _I, C.POINTER(_I)]),
+    "te_hier_bface_index": (_I, [_P, _I, _P]),
     "te_hier_placement": (_I, [_P, _PD, C.POINTER(_I), C.POINTER(_I)]),
     "te_hier_num_levels": (_I, [_P]),
     "te_hier_dim": (_I, [_P]),
@@ -84,6 +89,7 @@ SYMBOLS = {
     "te_gmg_stream": (_P, [_P]),
     "te_vec_create": (_I, [_P, _I, C.POINTER(_P)]),
     "te_vec_create_iface": (_I, [_P, _I, C.POINTER(_P)]),
+    "te_vec_create_boundary": (_I, [_P, _I, C.POINTER(_P)]),
     "te_vec_destroy": (None, [_P]),
     "te_vec_size": (C.c_size_t, [_P]),
     "te_vec_upload": (_I, [_P, _P]),
@@ -136,6 +142,9 @@ SYMBOLS = {
     "te_gmg_profile_select": (_I, [_P, C.c_char_p]),
     "te_gmg_profile_stride": (_I, [_P, _I]),
     "te_init_problem": (_I, [_P, _I, _I, _I, _P, _P]),
+    "te_add_boundary_rhs": (_I, [_P, _I, _P, _P]),
+    "te_boundary_sample": (_I, [_P, _I, _I, _P]),
+    "te_init_problem_sides": (_I, [_P, _I, _I, _P, _P]),
     "te_iface_interp": (_I, [_P, _I, _P, _P]),
     "te_apply_with_interface": (_I, [_P, _I, _P, _P, _P]),
     "te_add_iface_rhs": (_I, [_P, _I, _P, _P]),
@@ -239,14 +248,38 @@ class Mesh:
             self.h = None
 
 
+SIDES = ("west", "east", "south", "north", "bottom", "top")  # s = 2 * axis + upper (Side.h:51-56)
+
+
+def sides_mask(names):
+    """the bit mask of an iterable of side names"""
+    mask = 0
+    for s in names:
+        mask |= 1 << SIDES.index(s)
+    return mask
+
+
 class Hierarchy:
     """DomainGenerator + the CycleFactory level loop (ThundereggDomGen.h, CycleFactory3d.cpp:98-127)."""
 
-    def __init__(self, mesh, n, neumann=False, max_levels=0, patches_per_proc=0.0, rank=0, nranks=1, placement=None):
+    def __init__(self, mesh, n, neumann=False, max_levels=0, patches_per_proc=0.0, rank=0, nranks=1, placement=None, neumann_sides=None):
         """placement = (agglomerate, agglomerate_max, replicate) spelled out (a negative entry = the default), or None: the
-        environment's TE_AGGLOMERATE / TE_AGGLOMERATE_MAX / TE_REPLICATE, read once by te_hier_build"""
+        environment's TE_AGGLOMERATE / TE_AGGLOMERATE_MAX / TE_REPLICATE, read once by te_hier_build.
+        neumann_sides: one boundary kind per side of the domain (te_hier_build_bc) -- an int mask (bit 2 * axis + upper) or an
+        iterable of side names ("west", "east", "south", "north", "bottom", "top"); the other sides are Dirichlet"""
         self.h = C.c_void_p()
-        if placement is None:
+        if neumann_sides is not None:
+            if neumann:
+                raise ValueError("Hierarchy: give neumann or neumann_sides, not both")
+            mask = neumann_sides if isinstance(neumann_sides, (int, np.integer)) else sides_mask(neumann_sides)
+            if placement is None:  # (the environment's placement, as te_hier_build reads it)
+                e = os.environ.get
+                placement = (float(e("TE_AGGLOMERATE", -1.0)), int(e("TE_AGGLOMERATE_MAX", -1)),
+                             int(int(e("TE_REPLICATE")) != 0) if e("TE_REPLICATE") is not None else -1)
+            agg, cap, rep = placement
+            check(lib().te_hier_build_bc(mesh.h, n, int(mask), max_levels, float(patches_per_proc), rank, nranks,
+                                         float(agg), int(cap), int(rep), C.byref(self.h)))
+        elif placement is None:
             check(lib().te_hier_build(mesh.h, n, int(neumann), max_levels, float(patches_per_proc), rank, nranks,
                                       C.byref(self.h)))
         else:
@@ -254,7 +287,9 @@ class Hierarchy:
             check(lib().te_hier_build_placed(mesh.h, n, int(neumann), max_levels, float(patches_per_proc), rank, nranks,
                                              float(agg), int(cap), int(rep), C.byref(self.h)))
         self.n = n
-        self.neumann = bool(neumann)
+        self.neumann_sides = lib().te_hier_neumann_sides(self.h)
+        self.singular = bool(lib().te_hier_singular(self.h))
+        self.neumann = self.singular  # (true only when EVERY side is Neumann)
         self.dim = lib().te_hier_dim(self.h)
         self.num_levels = lib().te_hier_num_levels(self.h)
         self.rank, self.nranks = rank, nranks
@@ -301,6 +336,18 @@ class Hierarchy:
         check(lib().te_hier_iface_index(self.h, level, _ptr(out)))
         return out
 
+    def num_bfaces(self, level=0):
+        """this rank's physical faces on the level: the blocks of a boundary vector"""
+        out = C.c_int()
+        check(lib().te_hier_num_bfaces(self.h, level, C.byref(out)))
+        return out.value
+
+    def bface_index(self, level=0):
+        """[P_local][2*dim] the number of the physical face on side s of local patch p ((patch, side) order), -1 elsewhere"""
+        out = np.zeros((self.sizes(level)[0], 2 * self.dim), np.int32)
+        check(lib().te_hier_bface_index(self.h, level, _ptr(out)))
+        return out
+
     def l2g(self, level):
         out = np.zeros(self.sizes(level)[0], np.int32)
         check(lib().te_hier_level_l2g(self.h, level, _ptr(out)))
@@ -318,11 +365,13 @@ class Hierarchy:
 class Vec:
     """Vector<D> on the device (Vector.h:179-321); method names follow the reference."""
 
-    def __init__(self, gmg, level=0, data=None, iface=False):
-        """iface: an interface vector of the level (SchurHelper::getNewSchurVec), one block of n^(dim-1) per interface"""
-        self.gmg, self.level, self.iface = gmg, level, iface
+    def __init__(self, gmg, level=0, data=None, iface=False, boundary=False):
+        """iface: an interface vector of the level (SchurHelper::getNewSchurVec), one block of n^(dim-1) per interface;
+        boundary: a boundary vector (te_vec_create_boundary), one such block per physical face"""
+        self.gmg, self.level, self.iface = gmg, level, bool(iface or boundary)  # (iface: the blocks are faces, not patches)
         self.h = C.c_void_p()
-        check((lib().te_vec_create_iface if iface else lib().te_vec_create)(gmg.h, level, C.byref(self.h)))
+        create = lib().te_vec_create_boundary if boundary else (lib().te_vec_create_iface if iface else lib().te_vec_create)
+        check(create(gmg.h, level, C.byref(self.h)))
         if data is not None:
             self.upload(data)
 
@@ -436,6 +485,22 @@ class GMG:
 
     def new_iface_vector(self, level=0, data=None):
         return Vec(self, level, data, iface=True)
+
+    # ---- boundary data on the device (one kind per side of the domain: Hierarchy(neumann_sides=...))
+    def new_boundary_vector(self, level=0, data=None):
+        return Vec(self, level, data, boundary=True)
+
+    def add_boundary_rhs(self, bdata, f, level=0):
+        """f -= 2 g / h^2 on Dirichlet faces, f +- g_n / h on Neumann faces (Init.cpp:186-240, :89-146), in place"""
+        check(lib().te_add_boundary_rhs(self.h, level, bdata.h, f.h))
+
+    def boundary_sample(self, bdata, problem=0, level=0):
+        """the canned problems' boundary data: exact on Dirichlet faces, the derivative along the axis on Neumann faces"""
+        check(lib().te_boundary_sample(self.h, level, problem, bdata.h))
+
+    def init_problem_sides(self, f, exact=None, problem=0, level=0):
+        """init_problem with the kind of every physical face taken from the hierarchy's side mask"""
+        check(lib().te_init_problem_sides(self.h, level, problem, f.h, exact.h if exact is not None else None))
 
     # ---- the Schur-complement route (SchurHelper.h), single rank
     def iface_interp(self, u, gamma, level=0): check(lib().te_iface_interp(self.h, level, u.h, gamma.h))

@@ -98,6 +98,43 @@ int te_hier_build_placed(const te_mesh *m, int n, int neumann, int max_levels, d
 		return te::fail(TE_EINVAL, e.what());
 	}
 }
+// te_hier_build_placed with one boundary kind per side of the domain (bit s of neumann_sides = side s is Neumann)
+int te_hier_build_bc(const te_mesh *m, int n, int neumann_sides, int max_levels, double patches_per_proc,
+                     int rank, int nranks, double agglomerate, int agglomerate_max, int replicate, te_hier **out)
+{
+	if (!m || !out) return te::fail(TE_EINVAL, "te_hier_build_bc: null argument");
+	if (nranks < 1 || rank < 0 || rank >= nranks) return te::fail(TE_EINVAL, "te_hier_build_bc: rank outside [0, nranks)");
+	if (neumann_sides < 0 || neumann_sides >= (1 << (2 * m->tree.dim)))
+		return te::fail(TE_EINVAL, "te_hier_build_bc: neumann_sides has a bit at or above 2 * dim");
+	try {
+		te::Placement pl;
+		pl.agglomerate     = agglomerate;
+		pl.agglomerate_max = agglomerate_max;
+		pl.replicate       = replicate;
+		*out = new te_hier{te::Hierarchy::buildSides(m->tree, n, neumann_sides, max_levels, patches_per_proc, rank, nranks, pl)};
+		return TE_OK;
+	} catch (const std::exception &e) {
+		return te::fail(TE_EINVAL, e.what());
+	}
+}
+int te_hier_neumann_sides(const te_hier *h) { return h ? h->h.neumann_sides : TE_EINVAL; }
+int te_hier_singular(const te_hier *h) { return h ? (h->h.neumann_sides == (1 << (2 * h->h.dim)) - 1 ? 1 : 0) : TE_EINVAL; }
+int te_hier_num_bfaces(const te_hier *h, int level, int *out)
+{
+	if (!h || !out || level < 0 || level >= (int) h->h.levels.size()) return te::fail(TE_EINVAL, "te_hier_num_bfaces: bad argument");
+	std::vector<int32_t> idx;
+	*out = te::bfaceIndex(h->h.levels[level], idx);
+	return TE_OK;
+}
+int te_hier_bface_index(const te_hier *h, int level, int32_t *out)
+{
+	if (!h || level < 0 || level >= (int) h->h.levels.size() || (!out && h->h.levels[level].P > 0))
+		return te::fail(TE_EINVAL, "te_hier_bface_index: bad argument"); // (a rank without patches on the level may pass NULL)
+	std::vector<int32_t> idx;
+	te::bfaceIndex(h->h.levels[level], idx);
+	copyOut(out, idx);
+	return TE_OK;
+}
 // the placement of the small levels from the environment (each variable read here, once per call; unset = the default)
 int te_hier_build(const te_mesh *m, int n, int neumann, int max_levels, double patches_per_proc,
                   int rank, int nranks, te_hier **out)

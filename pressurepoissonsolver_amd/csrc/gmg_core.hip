@@ -54,6 +54,7 @@ int buildLevel(te_gmg *g, const Hierarchy &H, int li)
 	L->dim = T.dim, L->n = T.n, L->P = T.P, L->P_global = T.P_global, L->nc = T.nc, L->nf = T.nf;
 	L->replicated = T.replicated, L->gathered = T.gathered;
 	L->nif = T.nif, L->if_own = std::move(T.if_own), L->if_start = std::move(T.if_start), L->if_contrib = std::move(T.if_contrib);
+	L->nbf = T.nbf, L->bface_host = std::move(T.bface);
 	L->fx = std::move(T.fx), L->nremote = T.nremote;
 	L->nslots = T.nslots, L->ncf = T.ncf, L->n_int = T.n_int, L->n_bnd = T.n_bnd;
 	L->lds2d = T.lds2d, L->fuse2d = T.fuse2d, L->fuse2_ok = T.fuse2_ok;
@@ -165,6 +166,7 @@ int te_gmg_create(const te_hier *h, int device, te_gmg **out)
 		g->nranks = h->h.nranks;
 		g->placement[0] = h->h.agglomerate, g->placement[1] = h->h.agglomerate_max, g->placement[2] = h->h.replicate;
 		g->placement[3] = (double) h->h.levels.size();
+		g->placement[4] = (double) h->h.neumann_sides;
 		memset(g->calls, 0, sizeof(g->calls));
 		memset(g->cells, 0, sizeof(g->cells));
 		memset(g->total_ms, 0, sizeof(g->total_ms));
@@ -354,9 +356,9 @@ int te_init_problem(te_gmg *g, int level, int problem, int neumann, te_vec *f, t
 		Timed      t(g, KC_VECOP, f->n);
 #define TE_INIT(K, PROB)                                                                              \
 		if (neumann)                                                                                      \
-			hipLaunchKernelGGL((K<PROB, true>), grid, blk, 0, g->stream, G, f->d, e);                     \
+			hipLaunchKernelGGL((K<PROB, 1>), grid, blk, 0, g->stream, G, f->d, e);                     \
 		else                                                                                              \
-			hipLaunchKernelGGL((K<PROB, false>), grid, blk, 0, g->stream, G, f->d, e);
+			hipLaunchKernelGGL((K<PROB, 0>), grid, blk, 0, g->stream, G, f->d, e);
 		if (problem == PROBLEM_RANDOM) {
 			hipLaunchKernelGGL(k_init_random, grid, blk, 0, g->stream, G, L.nc, (uint64_t) 0x5EED, f->d, e);
 		} else if (problem == PROBLEM_TRIG) {
@@ -386,7 +388,7 @@ int te_vec_upload_patches(te_vec *v, int first_patch, int npatches, const double
 {
 	return guarded([&]() -> int {
 		if (!v || !host) return te::fail(TE_EINVAL, "te_vec_upload_patches: null");
-		const size_t nc = v->iface ? v->g->levels[v->level]->nf : v->g->levels[v->level]->nc; // (interface blocks)
+		const size_t nc = (v->iface || v->bnd) ? v->g->levels[v->level]->nf : v->g->levels[v->level]->nc; // (interface / boundary blocks)
 		if (first_patch < 0 || npatches < 0 || ((size_t) first_patch + npatches) * nc > v->n)
 			return te::fail(TE_EINVAL, "te_vec_upload_patches: patch range outside the vector");
 		if (npatches == 0) return TE_OK;
@@ -402,7 +404,7 @@ int te_vec_download_patches(const te_vec *v, int first_patch, int npatches, doub
 {
 	return guarded([&]() -> int {
 		if (!v || !host) return te::fail(TE_EINVAL, "te_vec_download_patches: null");
-		const size_t nc = v->iface ? v->g->levels[v->level]->nf : v->g->levels[v->level]->nc; // (interface blocks)
+		const size_t nc = (v->iface || v->bnd) ? v->g->levels[v->level]->nf : v->g->levels[v->level]->nc; // (interface / boundary blocks)
 		if (first_patch < 0 || npatches < 0 || ((size_t) first_patch + npatches) * nc > v->n)
 			return te::fail(TE_EINVAL, "te_vec_download_patches: patch range outside the vector");
 		if (npatches == 0) return TE_OK;

@@ -349,17 +349,19 @@ static int verifySchedule(te_gmg *g, const te_cycle_opts *o)
 static int checkPlacement(te_gmg *g)
 {
 	if (g->placement_checked || g->nranks < 2 || (!g->rccl.comm && !g->allreduce)) return TE_OK;
-	double hi[4], lo[4];
-	int    rc;
+	constexpr int NP = 5;
+	double        hi[NP], lo[NP];
+	int           rc;
 	for (int pass = 0; pass < 2; pass++) {
-		double v[4];
-		for (int k = 0; k < 4; k++) v[k] = pass ? -g->placement[k] : g->placement[k];
+		double v[NP];
+		for (int k = 0; k < NP; k++) v[k] = pass ? -g->placement[k] : g->placement[k];
 		HIPCHK(hipMemcpyAsync(g->result.p, v, sizeof v, hipMemcpyHostToDevice, g->stream));
-		if ((rc = finishReduce(g, 4, 1, true))) return rc;
-		for (int k = 0; k < 4; k++) (pass ? lo : hi)[k] = pass ? -g->result_host[k] : g->result_host[k];
+		if ((rc = finishReduce(g, NP, 1, true))) return rc;
+		for (int k = 0; k < NP; k++) (pass ? lo : hi)[k] = pass ? -g->result_host[k] : g->result_host[k];
 	}
-	static const char *what[4] = {"agglomerate (TE_AGGLOMERATE)", "agglomerate_max (TE_AGGLOMERATE_MAX)", "replicate (TE_REPLICATE)", "number of levels"};
-	for (int k = 0; k < 4; k++)
+	static const char *what[NP] = {"agglomerate (TE_AGGLOMERATE)", "agglomerate_max (TE_AGGLOMERATE_MAX)", "replicate (TE_REPLICATE)", "number of levels",
+	                               "the Neumann side mask (neumann_sides)"};
+	for (int k = 0; k < NP; k++)
 		if (hi[k] != lo[k]) {
 			char buf[256];
 			snprintf(buf, sizeof buf, "the ranks built different hierarchies: %s is %g on this rank (%d), between %g and %g over the ranks", what[k],

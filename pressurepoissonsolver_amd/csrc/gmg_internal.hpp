@@ -8,6 +8,7 @@
 //   gmg_launch2d.hip   the 2D twins
 //   gmg_cycle.hip      the cycle driver (GMG/Cycle.h, VCycle.h, WCycle.h), schedule check, te_gmg_autotune, per-operation entries
 //   gmg_krylov.hip     Vector<D> BLAS-1 entries and te_bicgstab (BiCGStab.h:45-106)
+//   gmg_bc.hip         boundary vectors, the fold of boundary data into a right-hand side, Init with a kind per side (bckernels.hpp)
 #pragma once
 #include "capi_common.hpp"
 #include "level_tables.hpp"
@@ -20,6 +21,7 @@
 #include "patchsolve32_sym.hpp"
 #include "patchsolve16.hpp"
 #include "initkernels.hpp"
+#include "bckernels.hpp"
 #include "pushkernels.hpp"
 #include <algorithm>
 #include <array>
@@ -56,6 +58,7 @@ struct te_vec {
 	double *d     = nullptr;
 	size_t  n     = 0;
 	bool    iface = false; // an interface vector of the level (te_vec_create_iface): num_ifaces * n^(dim-1) doubles
+	bool    bnd   = false; // a boundary vector of the level (te_vec_create_boundary): num_bfaces * n^(dim-1) doubles
 };
 
 namespace tei
@@ -224,6 +227,11 @@ struct LevelHost {
 	// interfaces (single rank; mesh.hpp Level::iface_*): host copies, uploaded by the Schur route at its first use (gmg_schur.hip)
 	int                  nif = -1;
 	std::vector<int32_t> if_own, if_start, if_contrib;
+	// physical faces (mesh.hpp bfaceIndex): this rank's, numbered in (patch, side) order; the device copy is made by the boundary-data
+	// calls at their first use (gmg_bc.hip)
+	int                  nbf = 0;
+	std::vector<int32_t> bface_host; // [P][2 dim], -1 on a face with a neighbour
+	DevBuf<int32_t>      bface;
 
 	Level2D dev2() const
 	{
@@ -407,7 +415,7 @@ struct te_gmg {
 	std::set<uint64_t>         verified_opts;
 	// how the hierarchy placed its small levels (te_hier_build: agglomerate, agglomerate_max, replicate) and its depth: every rank
 	// must have built the same (checked across the ranks before the first cycle, whatever TE_NO_VERIFY says)
-	double      placement[4]      = {0, 0, 0, 0};
+	double      placement[5]      = {0, 0, 0, 0, 0}; // ([4]: the Neumann side mask)
 	bool        placement_checked = false;
 	std::string autotune_report; // what te_gmg_autotune measured and chose
 	// watchdog: an exchange that has not completed TE_EXCHANGE_TIMEOUT seconds after it was issued ends the process.
@@ -562,7 +570,7 @@ inline int gridFor(size_t work_items, int tpb, int cap = 4096)
 	return (int) b;
 }
 
-inline bool sameShape(const te_vec *a, const te_vec *b) { return a && b && a->g == b->g && a->level == b->level && a->iface == b->iface; }
+inline bool sameShape(const te_vec *a, const te_vec *b) { return a && b && a->g == b->g && a->level == b->level && a->iface == b->iface && a->bnd == b->bnd; }
 
 // ---- gmg_core.hip
 int  newVec(te_gmg *g, int level, te_vec **out);
@@ -789,5 +797,6 @@ static inline int checkLevelVec(te_gmg *g, int level, const te_vec *v, const cha
 	if (!g || !v || level < 0 || level >= (int) g->levels.size() || v->g != g || v->level != level)
 		return te::fail(TE_EINVAL, std::string(who) + ": vector does not belong to this level");
 	if (v->iface) return te::fail(TE_EINVAL, std::string(who) + ": an interface vector where a domain vector is needed");
+	if (v->bnd) return te::fail(TE_EINVAL, std::string(who) + ": a boundary vector where a domain vector is needed");
 	return TE_OK;
 }

@@ -83,7 +83,10 @@ __device__ __forceinline__ double initCoord(double start, double h, int n, int i
 	return i == -1 ? start : (i == n ? start + h * n : start + h / 2.0 + h * i);
 }
 
-template <int PROB, bool NEUMANN> __global__ __launch_bounds__(256) void k_init3d(InitGeom G, double *__restrict__ f, double *__restrict__ exact)
+// KIND: every physical face Dirichlet (0) or Neumann (1) -- the drivers' one --neumann flag --, or INIT_SIDES: each face as the level's
+// face_kind says (te_init_problem_sides: one kind per side of the domain)
+constexpr int INIT_SIDES = 2;
+template <int PROB, int KIND> __global__ __launch_bounds__(256) void k_init3d(InitGeom G, double *__restrict__ f, double *__restrict__ exact)
 {
 	const int    n  = G.n;
 	const size_t nc = (size_t) n * n * n, total = nc * G.P;
@@ -101,7 +104,7 @@ template <int PROB, bool NEUMANN> __global__ __launch_bounds__(256) void k_init3
 			int o[3] = {ci[0], ci[1], ci[2]};
 			o[ax]    = hi ? n : -1;
 			const double bx = initCoord(st[0], h[0], n, o[0]), by = initCoord(st[1], h[1], n, o[1]), bz = initCoord(st[2], h[2], n, o[2]);
-			if (NEUMANN) {
+			if (KIND == INIT_SIDES ? G.face_kind[(size_t) p * 6 + s] == 1 /* FACE_NEUMANN */ : KIND == 1) {
 				const double g = Prob3<PROB>::normal(ax, bx, by, bz) / h[ax];
 				v              = hi ? v - g : v + g;
 			} else {
@@ -111,7 +114,7 @@ template <int PROB, bool NEUMANN> __global__ __launch_bounds__(256) void k_init3
 		f[i] = v;
 	}
 }
-template <int PROB, bool NEUMANN> __global__ __launch_bounds__(256) void k_init2d(InitGeom G, double *__restrict__ f, double *__restrict__ exact)
+template <int PROB, int KIND> __global__ __launch_bounds__(256) void k_init2d(InitGeom G, double *__restrict__ f, double *__restrict__ exact)
 {
 	const int    n  = G.n;
 	const size_t nc = (size_t) n * n, total = nc * G.P;
@@ -129,7 +132,7 @@ template <int PROB, bool NEUMANN> __global__ __launch_bounds__(256) void k_init2
 			int o[2] = {ci[0], ci[1]};
 			o[ax]    = hi ? n : -1;
 			const double bx = initCoord(st[0], h[0], n, o[0]), by = initCoord(st[1], h[1], n, o[1]);
-			if (NEUMANN) {
+			if (KIND == INIT_SIDES ? G.face_kind[(size_t) p * 4 + s] == 1 /* FACE_NEUMANN */ : KIND == 1) {
 				const double g = Prob2<PROB>::normal(ax, bx, by) / h[ax];
 				v              = hi ? v - g : v + g;
 			} else {

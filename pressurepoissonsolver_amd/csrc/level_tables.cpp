@@ -176,7 +176,7 @@ std::vector<RFace> exchangePlan(const Level &lv, int me, LevelTables &T)
 
 // the stencil tables, the ghost slot numbering, the interior / boundary order and the patch geometry. Returns the boundary key
 // of every patch-solve plan (T.plan[p] indexes it).
-std::vector<int> stencilTables(const Level &lv, int me, bool neumann, const std::vector<RFace> &recvs, LevelTables &T)
+std::vector<int> stencilTables(const Level &lv, int me, int neumann_sides, const std::vector<RFace> &recvs, LevelTables &T)
 {
 	const int D = lv.dim, n = lv.n, P = lv.P, NS = 2 * D, NQ = 1 << (D - 1);
 	std::map<std::tuple<int, int, int>, int> remote_slot; // (p, s, q) -> ghost slot
@@ -216,6 +216,7 @@ std::vector<int> stencilTables(const Level &lv, int me, bool neumann, const std:
 			const size_t gf   = (size_t) gp * NS + s;
 			const int    kind = lv.g_nbr_kind[gf];
 			if (kind == NBR_NONE) {
+				const bool neumann      = (neumann_sides >> s) & 1; // one kind per side of the DOMAIN
 				fk[p * NS + s]          = neumann ? FACE_NEUMANN : FACE_DIRICHLET;
 				T.face_kadj[p * NS + s] = neumann ? -1.0 : 1.0;
 				if (neumann) key |= 1 << s;
@@ -613,6 +614,7 @@ int computeLevelTables(const Hierarchy &H, int li, const LevelBuildOpts &opt, Le
 	T.if_own     = lv.iface_own;
 	T.if_start   = lv.iface_start;
 	T.if_contrib = lv.iface_contrib;
+	T.nbf        = te::bfaceIndex(lv, T.bface);
 	T.replicated = lv.replicated;
 	T.gathered   = lv.replicated || (H.nranks > 1 && std::all_of(lv.g_rank.begin(), lv.g_rank.end(), [&](int32_t r) { return r == lv.g_rank[0]; }));
 	T.nc         = (D == 3) ? (size_t) n * n * n : (size_t) n * n;
@@ -620,7 +622,7 @@ int computeLevelTables(const Hierarchy &H, int li, const LevelBuildOpts &opt, Le
 	const bool coarser = li + 1 < (int) H.levels.size();
 
 	const std::vector<RFace> recvs = exchangePlan(lv, H.rank, T);
-	const std::vector<int>   keys  = stencilTables(lv, H.rank, H.neumann, recvs, T);
+	const std::vector<int>   keys  = stencilTables(lv, H.rank, H.neumann_sides, recvs, T);
 	T.lds2d = (D == 2 && n <= 64 && n % 2 == 0 && !opt.simple_2d);
 	// see LevelHost::fuse2_ok: a global fact only. (Refined levels qualify: patches that copy through and
 	// coarse/fine faces -- whose ghost slots carry the interpolated value -- are handled by both kernels.)

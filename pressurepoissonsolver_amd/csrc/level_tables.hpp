@@ -54,6 +54,9 @@ struct LevelTables {
 	// interfaces (mesh.hpp Level::iface_*), passed through
 	int                  nif = -1;
 	std::vector<int32_t> if_own, if_start, if_contrib;
+	// physical faces (mesh.hpp bfaceIndex), passed through
+	int                  nbf = 0;
+	std::vector<int32_t> bface;
 };
 
 /// fills `out` for level li of H as rank H.rank sees it; TE_OK, or an error code with te::fail's message

@@ -191,6 +191,27 @@ LevelNodes collectLevel(const Tree &t, int L)
 }
 } // namespace
 
+Hierarchy Hierarchy::buildSides(const Tree &t, int n, int neumann_sides, int max_levels,
+                                double patches_per_proc, int rank, int nranks, const Placement &pl)
+{
+	const int all = (1 << (2 * t.dim)) - 1;
+	if (neumann_sides < 0 || neumann_sides > all) throw std::runtime_error("te::Hierarchy: neumann_sides has a bit at or above 2 * dim");
+	Hierarchy h     = build(t, n, neumann_sides == all, max_levels, patches_per_proc, rank, nranks, pl);
+	h.neumann_sides = neumann_sides;
+	return h;
+}
+
+int bfaceIndex(const Level &lv, std::vector<int32_t> &idx)
+{
+	const int NS = 2 * lv.dim;
+	int       nb = 0;
+	idx.assign((size_t) lv.P * NS, -1);
+	for (int p = 0; p < lv.P; p++)
+		for (int s = 0; s < NS; s++)
+			if (lv.g_nbr_kind[(size_t) lv.l2g[p] * NS + s] == NBR_NONE) idx[(size_t) p * NS + s] = nb++;
+	return nb;
+}
+
 Hierarchy Hierarchy::build(const Tree &t, int n, bool neumann, int max_levels,
                            double patches_per_proc, int rank, int nranks, const Placement &pl)
 {
@@ -202,6 +223,7 @@ Hierarchy Hierarchy::build(const Tree &t, int n, bool neumann, int max_levels,
 	h.rank    = rank;
 	h.nranks  = nranks;
 	h.neumann = neumann;
+	h.neumann_sides = neumann ? (1 << (2 * t.dim)) - 1 : 0;
 	const int dim = t.dim, nsides = 2 * dim, nq = 1 << (dim - 1);
 
 	std::vector<LevelNodes> lns;

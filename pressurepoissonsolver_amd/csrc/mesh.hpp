@@ -121,7 +121,9 @@ struct Hierarchy {
 	int                dim = 3;
 	int                n   = 0;
 	int                rank = 0, nranks = 1;
-	bool               neumann = false;
+	bool               neumann = false; ///< every side of the domain is Neumann (the constant null space)
+	/// bit s = the domain's side s (W,E,S,N,B,T) is a Neumann boundary, the others Dirichlet: one kind per side of the DOMAIN
+	int                neumann_sides = 0;
 	std::vector<Level> levels; ///< [0] = finest
 	/// placement of the small levels over the ranks (see Placement), as this hierarchy was built: part of what every rank
 	/// must agree on (te_gmg checks it across the ranks before the first cycle)
@@ -133,7 +135,15 @@ struct Hierarchy {
 	/// (max_levels <= 0 || built < max_levels) and patches/nranks >= patches_per_proc.
 	static Hierarchy build(const Tree &t, int n, bool neumann, int max_levels,
 	                       double patches_per_proc, int rank, int nranks, const Placement &pl = Placement());
+	/// the same with a kind per side; throws for a bit at or above 2 dim
+	static Hierarchy buildSides(const Tree &t, int n, int neumann_sides, int max_levels,
+	                            double patches_per_proc, int rank, int nranks, const Placement &pl = Placement());
 };
+
+/// This rank's physical faces of `lv` (no neighbour: NBR_NONE), numbered in (patch, side) order over its local patches:
+/// idx[P][2 dim] = the face's number, -1 on a face with a neighbour; returns how many there are. A level that lives on every
+/// rank is numbered whole on every rank.
+int bfaceIndex(const Level &lv, std::vector<int32_t> &idx);
 
 /// fills the interface tables of `lv` (all patches of the level, global order)
 void buildIfaces(Level &lv);

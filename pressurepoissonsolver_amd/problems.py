@@ -59,9 +59,15 @@ def gauss_normal(x, y, z):
             -12 * pi * np.sin(12 * pi * z) * np.exp(np.cos(12 * pi * z)) + 0 * x)
 
 
+def trig2d_normal(x, y):
+    """d/dx, d/dy of trig2d_exact (apps/2d/steady.cpp:317-318)"""
+    return (-2 * np.pi * np.sin(np.pi * y) * np.sin(2 * np.pi * x), np.pi * np.cos(np.pi * y) * np.cos(2 * np.pi * x))
+
+
 PROBLEMS = {"trig": (trig_rhs, trig_exact), "gauss": (gauss_rhs, gauss_exact)}
 NORMALS = {"trig": trig_normal, "gauss": gauss_normal}
 PROBLEMS_2D = {"trig": (trig2d_rhs, trig2d_exact)}
+NORMALS_2D = {"trig": trig2d_normal}
 
 
 def init_dirichlet_2d(tables, n, problem="trig", patches=None):
@@ -152,6 +158,94 @@ def init_neumann(tables, n, problem="trig", patches=None):
             gn = nfun(c[..., 0], c[..., 1], c[..., 2])[ax]
             f[k][tuple(sl)] += (-1.0 if up else 1.0) * gn / h[k, ax]
     return f.ravel(), ex.ravel()
+
+
+def init_sides(tables, n, sides, problem="trig", patches=None):
+    """(f, exact) flat vectors with one boundary kind per side of the domain: bit s of `sides` set = side s (2 * axis + upper)
+    is Neumann and takes Init::initNeumann's term, else Init::initDirichlet's. sides = 0 / 0b111111 give init_dirichlet /
+    init_neumann bit for bit (the same expressions in the same order)."""
+    ffun, efun = PROBLEMS[problem]
+    nfun = NORMALS[problem]
+    if patches is None:
+        patches = np.arange(len(tables["id"]))
+    cc = cell_centres(tables, n, patches)
+    f = ffun(cc[..., 0], cc[..., 1], cc[..., 2])
+    ex = efun(cc[..., 0], cc[..., 1], cc[..., 2])
+    h = tables["lengths"][patches] / n
+    for k, p in enumerate(patches):
+        for s in range(6):
+            if tables["nbr_kind"][p, s] != 0:
+                continue
+            ax, up = s // 2, s & 1
+            sl = [slice(None)] * 3
+            sl[2 - ax] = -1 if up else 0
+            c = cc[k][tuple(sl)].copy()
+            c[..., ax] += (0.5 if up else -0.5) * h[k, ax]  # the boundary face itself
+            if (sides >> s) & 1:
+                gn = nfun(c[..., 0], c[..., 1], c[..., 2])[ax]
+                f[k][tuple(sl)] += (-1.0 if up else 1.0) * gn / h[k, ax]
+            else:
+                f[k][tuple(sl)] -= 2 * efun(c[..., 0], c[..., 1], c[..., 2]) / h[k, ax] ** 2
+    return f.ravel(), ex.ravel()
+
+
+def init_sides_2d(tables, n, sides, problem="trig", patches=None):
+    """the 2D twin of init_sides (Init::initDirichlet2d / initNeumann2d, Init.cpp:304-361 / :246-303)"""
+    ffun, efun = PROBLEMS_2D[problem]
+    nfun = NORMALS_2D[problem]
+    if patches is None:
+        patches = np.arange(len(tables["id"]))
+    starts, lengths = tables["starts"], tables["lengths"]
+    idx = np.arange(n) + 0.5
+    f = np.empty((len(patches), n, n))
+    ex = np.empty_like(f)
+    for k, p in enumerate(patches):
+        h = lengths[p] / n
+        Y, X = np.meshgrid(starts[p, 1] + h[1] * idx, starts[p, 0] + h[0] * idx, indexing="ij")
+        f[k], ex[k] = ffun(X, Y), efun(X, Y)
+        for s in range(4):
+            if tables["nbr_kind"][p, s] != 0:
+                continue
+            ax, up = s // 2, s & 1
+            sl = [slice(None)] * 2
+            sl[1 - ax] = -1 if up else 0
+            xb, yb = X[tuple(sl)].copy(), Y[tuple(sl)].copy()
+            if ax == 0:
+                xb += (0.5 if up else -0.5) * h[0]
+            else:
+                yb += (0.5 if up else -0.5) * h[1]
+            if (sides >> s) & 1:
+                f[k][tuple(sl)] += (-1.0 if up else 1.0) * nfun(xb, yb)[ax] / h[ax]
+            else:
+                f[k][tuple(sl)] -= 2 * efun(xb, yb) / h[ax] ** 2
+    return f.ravel(), ex.ravel()
+
+
+def boundary_data(tables, n, sides, problem="trig", patches=None, dim=3):
+    """The problem's boundary data in boundary-vector layout (capi.GMG.new_boundary_vector): one block of n^(dim-1) values per
+    physical face of `patches` (default: all; a rank passes its Hierarchy.l2g) in (patch, side) order, the face's remaining axes
+    x-fastest; the exact solution on the face points of Dirichlet sides, its derivative along the axis on Neumann sides."""
+    if patches is None:
+        patches = np.arange(len(tables["id"]))
+    efun = (PROBLEMS if dim == 3 else PROBLEMS_2D)[problem][1]
+    nfun = (NORMALS if dim == 3 else NORMALS_2D)[problem]
+    out = []
+    idx = np.arange(n) + 0.5
+    for p in patches:
+        h = tables["lengths"][p] / n
+        st = tables["starts"][p]
+        for s in range(2 * dim):
+            if tables["nbr_kind"][p, s] != 0:
+                continue
+            ax, up = s // 2, s & 1
+            rest = [a for a in range(dim) if a != ax]
+            grids = np.meshgrid(*[st[a] + h[a] * idx for a in reversed(rest)], indexing="ij")  # (slowest axis first)
+            x = [None] * dim
+            for a, G in zip(reversed(rest), grids):
+                x[a] = G
+            x[ax] = np.full(grids[0].shape, st[ax] + (h[ax] * n if up else 0.0))
+            out.append((nfun(*x)[ax] if (sides >> s) & 1 else efun(*x)).ravel())
+    return np.concatenate(out) if out else np.zeros(0)
 
 
 def splitmix64_uniform(seed, count):

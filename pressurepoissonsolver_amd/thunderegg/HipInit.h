@@ -28,12 +28,14 @@ struct LevelGeometry { // this rank's patches of one level, in vector order (2D 
 	int                  n = 0, P = 0, dim = 3;
 	std::vector<double>  starts, lengths; // [P][dim]
 	std::vector<int32_t> nbr_kind;        // [P][2 dim], 0 = physical boundary
+	int                  neumann_sides = 0; // bit s = the domain's side s is Neumann (te_hier_build_bc); all bits for --neumann
 	LevelGeometry(const te_hier *h, int level)
 	{
 		int Pl = 0, Pg = 0;
 		if (te_hier_level_sizes(h, level, &Pl, &Pg) != TE_OK) throw 3;
 		n   = te_hier_n(h);
 		dim = te_hier_dim(h);
+		neumann_sides = te_hier_neumann_sides(h);
 		P   = Pl;
 		const int D = dim, NS = 2 * dim;
 		std::vector<double>  gs((size_t) Pg * D), gl((size_t) Pg * D);
@@ -119,6 +121,30 @@ inline void initNeumann(const LevelGeometry &G, std::shared_ptr<Vector<3>> f, st
 	detail::init<3>(G, f, exact, [&](const double *x) { return ffun(x[0], x[1], x[2]); }, [&](const double *x) { return efun(x[0], x[1], x[2]); },
 	                [&](int s, const double *x, double h) {
 		                const double g = (s / 2 == 0) ? nfunx(x[0], x[1], x[2]) : (s / 2 == 1 ? nfuny(x[0], x[1], x[2]) : nfunz(x[0], x[1], x[2]));
+		                return (s & 1) ? -(g / h) : g / h;
+	                });
+}
+/// One boundary kind per side of the domain (LevelGeometry::neumann_sides, set from a driver's per-side IsNeumann): the common loop
+/// with the branch taken per face -- Init::initNeumann's term (Init.cpp:89-146) on the Neumann sides, Init::initDirichlet's
+/// (:186-240) on the others. Mask 0 / all bits = initDirichlet / initNeumann.
+inline void initSides(const LevelGeometry &G, std::shared_ptr<Vector<3>> f, std::shared_ptr<Vector<3>> exact, detail::Fun3 ffun, detail::Fun3 efun,
+                      detail::Fun3 nfunx, detail::Fun3 nfuny, detail::Fun3 nfunz)
+{
+	detail::init<3>(G, f, exact, [&](const double *x) { return ffun(x[0], x[1], x[2]); }, [&](const double *x) { return efun(x[0], x[1], x[2]); },
+	                [&](int s, const double *x, double h) {
+		                if (!((G.neumann_sides >> s) & 1)) return -(2 * efun(x[0], x[1], x[2]) / (h * h));
+		                const double g = (s / 2 == 0) ? nfunx(x[0], x[1], x[2]) : (s / 2 == 1 ? nfuny(x[0], x[1], x[2]) : nfunz(x[0], x[1], x[2]));
+		                return (s & 1) ? -(g / h) : g / h;
+	                });
+}
+/// the 2D twin (Init.cpp:246-303 / :304-361)
+inline void initSides2d(const LevelGeometry &G, std::shared_ptr<Vector<2>> f, std::shared_ptr<Vector<2>> exact, detail::Fun2 ffun, detail::Fun2 efun,
+                        detail::Fun2 nfunx, detail::Fun2 nfuny)
+{
+	detail::init<2>(G, f, exact, [&](const double *x) { return ffun(x[0], x[1]); }, [&](const double *x) { return efun(x[0], x[1]); },
+	                [&](int s, const double *x, double h) {
+		                if (!((G.neumann_sides >> s) & 1)) return -(efun(x[0], x[1]) * 2 / (h * h));
+		                const double g = (s / 2 == 0) ? nfunx(x[0], x[1]) : nfuny(x[0], x[1]);
 		                return (s & 1) ? -(g / h) : g / h;
 	                });
 }
