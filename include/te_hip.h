@@ -171,6 +171,14 @@ int    te_vec_create_iface(te_gmg *g, int level, te_vec **out);
  * te_vec_download_patches count blocks); the domain operators refuse it with TE_EINVAL. Exists on sharded hierarchies too.
  * Replaces nothing in the reference (its boundary data are std::function callbacks evaluated inside Init.cpp's loops). */
 int    te_vec_create_boundary(te_gmg *g, int level, te_vec **out);
+/* A face vector of `level`: one component per cell face, ALONG THE AXIS (not the outward normal), stored per local patch -- a face
+ * shared by two patches is stored by both. Per patch, D = dim, n = cells per axis, D n^D + D n^(D-1) doubles in this order:
+ * blocks LO_a, a = 0..D-1, n^D doubles each in the cell layout of a domain vector (x fastest): the component on the LOWER a-face
+ * of the cell; then blocks HI_a, a = 0..D-1, n^(D-1) doubles each, laid out like an interface / boundary block of side 2a+1: the
+ * component on the patch's UPPER a-face. Zero-filled. Every te_vec_* call takes it (te_vec_upload_patches / _download_patches
+ * count patches); the domain operators refuse it with TE_EINVAL; te_gradient, te_divergence and te_project refuse anything else
+ * in its place. Exists on sharded hierarchies (local patches) and on every level. Replaces nothing in the reference. */
+int    te_vec_create_faces(te_gmg *g, int level, te_vec **out);
 void   te_vec_destroy(te_vec *v);
 size_t te_vec_size(const te_vec *v);                 /* doubles (local patches * n^dim) */
 int    te_vec_upload(te_vec *v, const double *host); /* Vector<D>::getLocalData write path */
@@ -390,6 +398,25 @@ int te_boundary_sample(te_gmg *g, int level, int problem, te_vec *bdata);
  * Init::initDirichlet's term on Dirichlet faces and Init::initNeumann's on Neumann faces in one pass (for mask 0 / all bits the
  * very bits of te_init_problem with neumann = 0 / 1). */
 int te_init_problem_sides(te_gmg *g, int level, int problem, te_vec *f, te_vec *exact);
+
+/* The operators that turn a pressure into a velocity correction, consistent with te_apply's discrete Laplacian (a flow solver's
+ * projection step: f = div(u*) / dt before the solve, u = u* - dt grad(p) after it). They replace nothing in the reference.
+ * h_a = the patch's spacing on axis a, m = the cell just inside a patch face:
+ *   G = grad u     interior face between cells c - e_a and c: (u[c] - u[c - e_a]) / h_a; patch face with a neighbour: (m - ghost) / h_a
+ *                  below, (ghost - m) / h_a above, ghost = exactly the value te_apply uses there (same level: the neighbour's cell,
+ *                  local or received; coarse/fine: 2 gamma - m with TriLinInterp / BilinearInterpolator's gamma); physical Dirichlet
+ *                  face: ghost = 2 g - m; physical Neumann face: G = g_n. g / g_n come from the boundary vector `bdata` of the same
+ *                  level (NULL: zero).
+ *   out = alpha div U    out[c] = alpha * sum_a (U_a(upper a-face of c) - LO_a[c]) / h_a; patch-local, no exchange.
+ *   U -= alpha grad p    te_project: one fused pass, the gradient is never stored.
+ * te_divergence(1, te_gradient(u, bdata)) equals te_apply(u) minus what te_add_boundary_rhs(bdata, .) adds to a zero vector, up to
+ * rounding. Both copies of a same-level face receive the same bits (one rank or several); on a coarse/fine face the two sides differ
+ * by construction (the operator is not flux-matched there). te_gradient and te_project are collective on a sharded hierarchy (they
+ * make the ghosts current as te_apply does); te_divergence is local. TE_EINVAL: NULL, another solver's or level's vector, a vector
+ * of the wrong kind (u, p, out: domain vectors; G, U: face vectors; bdata: a boundary vector or NULL). */
+int te_gradient(te_gmg *g, int level, const te_vec *u, const te_vec *bdata, te_vec *G);
+int te_divergence(te_gmg *g, int level, double alpha, const te_vec *U, te_vec *out);
+int te_project(te_gmg *g, int level, double alpha, const te_vec *p, const te_vec *bdata, te_vec *U);
 
 /* kernel timing hooks for bench.py: HIP-event time of the last te_vcycle's dominant kernel */
 int te_gmg_profile(te_gmg *g, int enable);

@@ -90,6 +90,7 @@ SYMBOLS = {
     "te_vec_create": (_I, [_P, _I, C.POINTER(_P)]),
     "te_vec_create_iface": (_I, [_P, _I, C.POINTER(_P)]),
     "te_vec_create_boundary": (_I, [_P, _I, C.POINTER(_P)]),
+    "te_vec_create_faces": (_I, [_P, _I, C.POINTER(_P)]),
     "te_vec_destroy": (None, [_P]),
     "te_vec_size": (C.c_size_t, [_P]),
     "te_vec_upload": (_I, [_P, _P]),
@@ -152,6 +153,9 @@ SYMBOLS = {
     "te_schur_apply": (_I, [_P, _I, _P, _P]),
     "te_schur_cheb": (_I, [_P, _I, _P, _P]),
     "te_schur_solve": (_I, [_P, _I, _I, _P, _P, _P, _I, _D, C.POINTER(_I), _PD]),
+    "te_gradient": (_I, [_P, _I, _P, _P, _P]),
+    "te_divergence": (_I, [_P, _I, _D, _P, _P]),
+    "te_project": (_I, [_P, _I, _D, _P, _P, _P]),
     "te_integrate": (_I, [_P, _I, _P, _P]),
     "te_volume": (_I, [_P, _I, _P]),
 }
@@ -362,15 +366,34 @@ class Hierarchy:
             self.h = None
 
 
+def face_vector_size(n, dim):
+    """doubles per patch of a face vector (te_vec_create_faces)"""
+    return dim * n ** dim + dim * n ** (dim - 1)
+
+
+def face_vector_views(a, n, dim):
+    """the host array of a face vector as (lo[P, dim, n..n], hi[P, dim, n^(dim-1)]): lo[p, a] = the components on the lower
+    a-faces of patch p's cells (numpy index order z, y, x), hi[p, a] = those on the patch's upper a-face. Views: writing
+    through them changes `a`."""
+    a = np.asarray(a)
+    per = a.reshape(-1, face_vector_size(n, dim))
+    nlo = dim * n ** dim
+    return per[:, :nlo].reshape((-1, dim) + (n,) * dim), per[:, nlo:].reshape((-1, dim, n ** (dim - 1)))
+
+
 class Vec:
     """Vector<D> on the device (Vector.h:179-321); method names follow the reference."""
 
-    def __init__(self, gmg, level=0, data=None, iface=False, boundary=False):
+    def __init__(self, gmg, level=0, data=None, iface=False, boundary=False, faces=False):
         """iface: an interface vector of the level (SchurHelper::getNewSchurVec), one block of n^(dim-1) per interface;
-        boundary: a boundary vector (te_vec_create_boundary), one such block per physical face"""
+        boundary: a boundary vector (te_vec_create_boundary), one such block per physical face;
+        faces: a face vector (te_vec_create_faces), dim n^dim + dim n^(dim-1) doubles per patch"""
         self.gmg, self.level, self.iface = gmg, level, bool(iface or boundary)  # (iface: the blocks are faces, not patches)
+        self.faces = bool(faces)
         self.h = C.c_void_p()
         create = lib().te_vec_create_boundary if boundary else (lib().te_vec_create_iface if iface else lib().te_vec_create)
+        if faces:
+            create = lib().te_vec_create_faces
         check(create(gmg.h, level, C.byref(self.h)))
         if data is not None:
             self.upload(data)
@@ -390,16 +413,20 @@ class Vec:
         check(lib().te_vec_download(self.h, _ptr(out)))
         return out
 
+    def _block(self):
+        n, d = self.gmg.hier.n, self.gmg.hier.dim
+        return face_vector_size(n, d) if getattr(self, "faces", False) else n ** (d - self.iface)
+
     def upload_patches(self, first, a):
         """Vector<D>::getLocalData(i) write path for a run of patches"""
         a = np.ascontiguousarray(a, dtype=np.float64)
-        nc = self.gmg.hier.n ** (self.gmg.hier.dim - self.iface)
+        nc = self._block()
         if a.size % nc:
             raise ValueError("upload_patches: not a whole number of patches")
         check(lib().te_vec_upload_patches(self.h, first, a.size // nc, _ptr(a.ravel())))
 
     def download_patches(self, first, count):
-        out = np.empty(count * self.gmg.hier.n ** (self.gmg.hier.dim - self.iface), np.float64)
+        out = np.empty(count * self._block(), np.float64)
         check(lib().te_vec_download_patches(self.h, first, count, _ptr(out)))
         return out
 
@@ -489,6 +516,22 @@ class GMG:
     # ---- boundary data on the device (one kind per side of the domain: Hierarchy(neumann_sides=...))
     def new_boundary_vector(self, level=0, data=None):
         return Vec(self, level, data, boundary=True)
+
+    # ---- MAC gradient, divergence, pressure projection (te_hip.h: they replace nothing in the reference)
+    def new_face_vector(self, level=0, data=None):
+        return Vec(self, level, data, faces=True)
+
+    def gradient(self, u, G, bdata=None, level=0):
+        """G = grad u on the cell faces, ghosts as te_apply reads them, boundary data from `bdata` (None: zero); collective"""
+        check(lib().te_gradient(self.h, level, u.h, bdata.h if bdata is not None else None, G.h))
+
+    def divergence(self, U, out, alpha=1.0, level=0):
+        """out = alpha div U (patch-local)"""
+        check(lib().te_divergence(self.h, level, float(alpha), U.h, out.h))
+
+    def project(self, U, p, alpha=1.0, bdata=None, level=0):
+        """U -= alpha grad p in one pass; collective"""
+        check(lib().te_project(self.h, level, float(alpha), p.h, bdata.h if bdata is not None else None, U.h))
 
     def add_boundary_rhs(self, bdata, f, level=0):
         """f -= 2 g / h^2 on Dirichlet faces, f +- g_n / h on Neumann faces (Init.cpp:186-240, :89-146), in place"""

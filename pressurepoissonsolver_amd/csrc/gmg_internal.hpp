@@ -9,6 +9,7 @@
 //   gmg_cycle.hip      the cycle driver (GMG/Cycle.h, VCycle.h, WCycle.h), schedule check, te_gmg_autotune, per-operation entries
 //   gmg_krylov.hip     Vector<D> BLAS-1 entries and te_bicgstab (BiCGStab.h:45-106)
 //   gmg_bc.hip         boundary vectors, the fold of boundary data into a right-hand side, Init with a kind per side (bckernels.hpp)
+//   gmg_projection.hip face vectors, MAC gradient, divergence, pressure projection (projkernels.hpp)
 #pragma once
 #include "capi_common.hpp"
 #include "level_tables.hpp"
@@ -59,6 +60,7 @@ struct te_vec {
 	size_t  n     = 0;
 	bool    iface = false; // an interface vector of the level (te_vec_create_iface): num_ifaces * n^(dim-1) doubles
 	bool    bnd   = false; // a boundary vector of the level (te_vec_create_boundary): num_bfaces * n^(dim-1) doubles
+	bool    faces = false; // a face vector of the level (te_vec_create_faces): per local patch dim n^dim + dim n^(dim-1) doubles
 };
 
 namespace tei
@@ -78,7 +80,9 @@ enum KClass : int {
 	KC_BICG_UPDATE, KC_BICG_S, KC_BICG_P, KC_APPLY_DOT,
 	// the patch-local Krylov solve of PatchSolvers/BiCGStabSolver.h (2D): compute-resident, its HBM bytes are one read of the
 	// right-hand side and a read + write of the patch (24 B/site) whatever the iteration count
-	KC_PATCH_BCGS, KC_COUNT
+	KC_PATCH_BCGS,
+	// the MAC operators of projkernels.hpp (34.25 / 32.75 / 59 B per site at 32^3 patches)
+	KC_GRADIENT, KC_DIVERGENCE, KC_PROJECT, KC_COUNT
 };
 extern const char *kclassName[KC_COUNT]; // (gmg_core.hip)
 
@@ -570,7 +574,7 @@ inline int gridFor(size_t work_items, int tpb, int cap = 4096)
 	return (int) b;
 }
 
-inline bool sameShape(const te_vec *a, const te_vec *b) { return a && b && a->g == b->g && a->level == b->level && a->iface == b->iface && a->bnd == b->bnd; }
+inline bool sameShape(const te_vec *a, const te_vec *b) { return a && b && a->g == b->g && a->level == b->level && a->iface == b->iface && a->bnd == b->bnd && a->faces == b->faces; }
 
 // ---- gmg_core.hip
 int  newVec(te_gmg *g, int level, te_vec **out);
@@ -688,6 +692,7 @@ int patchSolve(te_gmg *g, LevelHost &L, const double *f, double *u, bool zero_gu
 int doRestrict(te_gmg *g, int fine_level, const double *fine, double *coarse);
 int doProlong(te_gmg *g, int fine_level, const double *coarse, double *fine);
 // ---- gmg_launch2d.hip
+int prepareGhosts2d(te_gmg *g, LevelHost &L, const double *u);
 template <int MODE> int launchStencil2d(te_gmg *g, LevelHost &L, const double *u, const double *f, double *out, double omega, int redmode = RED_NONE,
                                         const double *red_a = nullptr, int *red_items = nullptr);
 extern template int launchStencil2d<MODE_APPLY>(te_gmg *, LevelHost &, const double *, const double *, double *, double, int, const double *, int *);
@@ -773,6 +778,14 @@ template <int OP> int reduce(const te_vec *a, const te_vec *b, double *out, bool
 	return TE_OK;
 }
 
+// doubles per block of te_vec_upload_patches / _download_patches: a patch of a domain or face vector, a face of the other kinds
+inline size_t vecBlock(const te_vec *v)
+{
+	const LevelHost &L = *v->g->levels[v->level];
+	if (v->faces) return (size_t) L.dim * L.nc + (size_t) L.dim * L.nf;
+	return (v->iface || v->bnd) ? L.nf : L.nc;
+}
+
 inline void swapData(te_vec *a, te_vec *b) { std::swap(a->d, b->d); }
 
 } // namespace tei
@@ -798,5 +811,6 @@ static inline int checkLevelVec(te_gmg *g, int level, const te_vec *v, const cha
 		return te::fail(TE_EINVAL, std::string(who) + ": vector does not belong to this level");
 	if (v->iface) return te::fail(TE_EINVAL, std::string(who) + ": an interface vector where a domain vector is needed");
 	if (v->bnd) return te::fail(TE_EINVAL, std::string(who) + ": a boundary vector where a domain vector is needed");
+	if (v->faces) return te::fail(TE_EINVAL, std::string(who) + ": a face vector where a domain vector is needed");
 	return TE_OK;
 }

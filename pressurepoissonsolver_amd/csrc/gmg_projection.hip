@@ -1,0 +1,178 @@
+// Face vectors and the MAC operators on them: gradient of a cell vector, divergence of a face vector, pressure projection
+// (projkernels.hpp; see gmg_internal.hpp). The gradient and the projection make the level's ghosts current exactly as te_apply
+// does (withGhosts / prepareGhosts2d): collective on a sharded hierarchy. The divergence reads only its own patches.
+#include "gmg_ghosts3d.hpp"
+#include "projkernels.hpp"
+
+namespace tei
+{
+static int checkFaceVec(te_gmg *g, int level, const te_vec *v, const char *who)
+{
+	if (!g || !v || level < 0 || level >= (int) g->levels.size() || v->g != g || v->level != level || !v->faces)
+		return te::fail(TE_EINVAL, std::string(who) + ": not a face vector of this level");
+	return TE_OK;
+}
+static int checkBdata(te_gmg *g, int level, const te_vec *v, const char *who)
+{
+	if (v && (!g || v->g != g || v->level != level || !v->bnd)) return te::fail(TE_EINVAL, std::string(who) + ": bdata is not a boundary vector of this level");
+	return TE_OK;
+}
+
+static int faceGeom(LevelHost &L, const te_vec *bdata, FaceGeom *F)
+{
+	int rc;
+	F->h = L.geom_h.p, F->bface = nullptr, F->bdata = nullptr;
+	if (!bdata || L.nbf == 0) return TE_OK;
+	if (!L.bface.p && !L.bface_host.empty() && (rc = L.bface.upload(L.bface_host))) return rc;
+	F->bface = L.bface.p, F->bdata = bdata->d;
+	return TE_OK;
+}
+
+// z-slabs per patch on levels with few patches: the rule of launchStencilN
+template <int N> static int projSlabs(const te_gmg *g, int P)
+{
+	int zs = 1;
+	if (N >= 8) {
+		while (zs < 4 && (g->cfg.has(O_ZS_FORCE) || (size_t) P * zs < 2048) && N / (zs * 2) >= 4) zs *= 2;
+		if (zs == 4 && N == 32 && P <= 64 && !g->cfg.has(O_NO_ZS8)) zs = 8;
+	}
+	return zs;
+}
+
+template <int N, bool PROJECT> static int gradientN(te_gmg *g, LevelHost &L, const FaceGeom &F, const double *u, double *G, double alpha)
+{
+	const int zs     = projSlabs<N>(g, L.P);
+	auto      launch = [&](LevelDev D) {
+        if (D.count == 0) return;
+        Timed      t(g, PROJECT ? KC_PROJECT : KC_GRADIENT, (size_t) D.count * L.nc);
+        const dim3 grid(8 * ((D.count * zs + 7) / 8)), blk(Tile3<N>::TPB);
+        switch (zs) {
+            case 1: hipLaunchKernelGGL((k_gradient3d<N, PROJECT, 1>), grid, blk, 0, g->stream, D, F, u, G, alpha); break;
+            case 2:
+                if constexpr (N >= 8) hipLaunchKernelGGL((k_gradient3d<N, PROJECT, 2>), grid, blk, 0, g->stream, D, F, u, G, alpha);
+                break;
+            case 8:
+                if constexpr (N >= 32) hipLaunchKernelGGL((k_gradient3d<N, PROJECT, 8>), grid, blk, 0, g->stream, D, F, u, G, alpha);
+                break;
+            default:
+                if constexpr (N >= 16) hipLaunchKernelGGL((k_gradient3d<N, PROJECT, 4>), grid, blk, 0, g->stream, D, F, u, G, alpha);
+                break;
+        }
+	};
+	int rc = withGhosts<N>(g, L, u, launch);
+	if (rc) return rc;
+	HIPCHK(hipGetLastError());
+	return TE_OK;
+}
+
+template <bool PROJECT> static int gradient(te_gmg *g, LevelHost &L, const te_vec *u, const te_vec *bdata, te_vec *G, double alpha)
+{
+	if (L.P == 0) return TE_OK;
+	FaceGeom F;
+	int      rc = faceGeom(L, bdata, &F);
+	if (rc) return rc;
+	if (L.dim == 2) {
+		if ((rc = prepareGhosts2d(g, L, u->d))) return rc;
+		Timed t(g, PROJECT ? KC_PROJECT : KC_GRADIENT, (size_t) L.P * L.nc);
+		hipLaunchKernelGGL(k_gradient2d<PROJECT>, dim3(gridFor((size_t) L.P * L.nc / 2, 256, 65536)), dim3(256), 0, g->stream, L.dev2(), F,
+		                   (const double *) u->d, G->d, alpha);
+		HIPCHK(hipGetLastError());
+		return TE_OK;
+	}
+	switch (L.n) {
+		case 4: return gradientN<4, PROJECT>(g, L, F, u->d, G->d, alpha);
+		case 8: return gradientN<8, PROJECT>(g, L, F, u->d, G->d, alpha);
+		case 16: return gradientN<16, PROJECT>(g, L, F, u->d, G->d, alpha);
+		default: return gradientN<32, PROJECT>(g, L, F, u->d, G->d, alpha);
+	}
+}
+
+template <int N> static void divergenceN(te_gmg *g, LevelHost &L, const double *U, double *out, double alpha)
+{
+	const int  zs = projSlabs<N>(g, L.P);
+	const dim3 grid(8 * ((L.P * zs + 7) / 8)), blk(Tile3<N>::TPB);
+	switch (zs) {
+		case 1: hipLaunchKernelGGL((k_divergence3d<N, 1>), grid, blk, 0, g->stream, L.P, L.geom_h.p, U, out, alpha); break;
+		case 2:
+			if constexpr (N >= 8) hipLaunchKernelGGL((k_divergence3d<N, 2>), grid, blk, 0, g->stream, L.P, L.geom_h.p, U, out, alpha);
+			break;
+		case 8:
+			if constexpr (N >= 32) hipLaunchKernelGGL((k_divergence3d<N, 8>), grid, blk, 0, g->stream, L.P, L.geom_h.p, U, out, alpha);
+			break;
+		default:
+			if constexpr (N >= 16) hipLaunchKernelGGL((k_divergence3d<N, 4>), grid, blk, 0, g->stream, L.P, L.geom_h.p, U, out, alpha);
+			break;
+	}
+}
+} // namespace tei
+
+extern "C" {
+int te_vec_create_faces(te_gmg *g, int level, te_vec **out)
+{
+	return guarded([&]() -> int {
+		if (!g || !out || level < 0 || level >= (int) g->levels.size()) return te::fail(TE_EINVAL, "te_vec_create_faces: bad argument");
+		LevelHost &L = *g->levels[level];
+		HIPCHK(hipSetDevice(g->device));
+		auto v   = std::make_unique<te_vec>();
+		v->g     = g;
+		v->level = level;
+		v->faces = true;
+		v->n     = (size_t) L.P * ((size_t) L.dim * L.nc + (size_t) L.dim * L.nf);
+		HIPCHK(hipMalloc(&v->d, sizeof(double) * std::max<size_t>(v->n, 2)));
+		hipError_t e = hipMemsetAsync(v->d, 0, sizeof(double) * v->n, g->stream);
+		if (e != hipSuccess) {
+			(void) hipFree(v->d);
+			return te::fail(TE_EHIP, std::string("hipMemsetAsync: ") + hipGetErrorString(e));
+		}
+		*out = v.release();
+		return TE_OK;
+	});
+}
+
+int te_gradient(te_gmg *g, int level, const te_vec *u, const te_vec *bdata, te_vec *G)
+{
+	return guarded([&]() -> int {
+		int rc;
+		if ((rc = checkLevelVec(g, level, u, "te_gradient")) || (rc = checkBdata(g, level, bdata, "te_gradient"))
+		    || (rc = checkFaceVec(g, level, G, "te_gradient")))
+			return rc;
+		return gradient<false>(g, *g->levels[level], u, bdata, G, 0.0);
+	});
+}
+
+int te_project(te_gmg *g, int level, double alpha, const te_vec *p, const te_vec *bdata, te_vec *U)
+{
+	return guarded([&]() -> int {
+		int rc;
+		if ((rc = checkLevelVec(g, level, p, "te_project")) || (rc = checkBdata(g, level, bdata, "te_project"))
+		    || (rc = checkFaceVec(g, level, U, "te_project")))
+			return rc;
+		return gradient<true>(g, *g->levels[level], p, bdata, U, alpha);
+	});
+}
+
+int te_divergence(te_gmg *g, int level, double alpha, const te_vec *U, te_vec *out)
+{
+	return guarded([&]() -> int {
+		int rc;
+		if ((rc = checkFaceVec(g, level, U, "te_divergence")) || (rc = checkLevelVec(g, level, out, "te_divergence"))) return rc;
+		LevelHost &L = *g->levels[level];
+		if (L.P == 0) return TE_OK;
+		if (L.xf_valid_for == out->d) L.xf_valid_for = nullptr; // out changes
+		Timed t(g, KC_DIVERGENCE, (size_t) L.P * L.nc);
+		if (L.dim == 2) {
+			hipLaunchKernelGGL(k_divergence2d, dim3(gridFor((size_t) L.P * L.nc / 2, 256, 65536)), dim3(256), 0, g->stream, L.P, L.n, L.geom_h.p,
+			                   (const double *) U->d, out->d, alpha);
+		} else {
+			switch (L.n) {
+				case 4: divergenceN<4>(g, L, U->d, out->d, alpha); break;
+				case 8: divergenceN<8>(g, L, U->d, out->d, alpha); break;
+				case 16: divergenceN<16>(g, L, U->d, out->d, alpha); break;
+				default: divergenceN<32>(g, L, U->d, out->d, alpha); break;
+			}
+		}
+		HIPCHK(hipGetLastError());
+		return TE_OK;
+	});
+}
+} // extern "C"

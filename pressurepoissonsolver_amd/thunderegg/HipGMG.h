@@ -16,6 +16,9 @@
 //   HipSchurOp<D>      : Operator<D-1>        y = x - T x, the Schur operator (Operators/SchurWrapOp.h with its identity
 //                                             term); rhs() = g = Interp(Solve(f, 0)), solution() = u = Solve(f, gamma)
 //   HipChebPrec<D>     : Operator<D-1>        PolyChebPrec::apply (PolyChebPrec.cpp)
+// The MAC operators of a projection step (te_gradient / te_divergence / te_project; they replace nothing in the reference):
+//   HipFaceVector<D>   : (no base)            RAII face vector (te_vec_create_faces), host transfer by whole patches
+//   gradient / divergence / project           free functions taking HipVector<D> and HipFaceVector<D>
 //
 // Error convention: the reference throws `int` (`throw 3;`, e.g. GMG/InterLevelComm.h:175,
 // SchurHelper.h:129); a non-zero te_* status is rethrown the same way.
@@ -333,5 +336,52 @@ template <size_t D> class HipChebPrec : public Operator<D - 1>
 		check(te_schur_cheb(ctx->g, level, HipVector<D - 1>::raw(x), const_cast<te_vec *>(HipVector<D - 1>::raw(b))));
 	}
 };
+// ------------------------------------------------------------------------- MAC gradient, divergence, projection
+/// A face vector of one level (te_vec_create_faces): per local patch D n^D + D n^(D-1) doubles -- the blocks LO_0 .. LO_{D-1}
+/// (n^D each, cell layout: the component on the lower a-face of the cell), then HI_0 .. HI_{D-1} (n^(D-1) each: the patch's upper
+/// a-face). Not a Vector<D>: the reference has no face-centred vector. Every te_vec_* BLAS-1 call takes raw().
+template <size_t D> class HipFaceVector
+{
+	public:
+	std::shared_ptr<Context> ctx;
+	te_vec                  *v = nullptr;
+	int                      level;
+	HipFaceVector(std::shared_ptr<Context> ctx_, int level_ = 0) : ctx(ctx_), level(level_) { check(te_vec_create_faces(ctx->g, level, &v)); }
+	~HipFaceVector() { te_vec_destroy(v); }
+	HipFaceVector(const HipFaceVector &) = delete;
+	HipFaceVector &operator=(const HipFaceVector &) = delete;
+	te_vec        *raw() const { return v; }
+	/// values on one face of a patch, n^(D-1)
+	size_t faceSize() const
+	{
+		size_t nf = 1;
+		for (size_t i = 1; i < D; i++) nf *= ctx->n;
+		return nf;
+	}
+	/// doubles per patch
+	size_t patchSize() const { return D * faceSize() * ctx->n + D * faceSize(); }
+	int    numLocalPatches() const { return (int) (te_vec_size(v) / patchSize()); }
+	/// where block LO_a / HI_a starts inside a patch's run of doubles
+	size_t loOffset(int a) const { return (size_t) a * faceSize() * ctx->n; }
+	size_t hiOffset(int a) const { return D * faceSize() * ctx->n + (size_t) a * faceSize(); }
+	void upload(int first_patch, int npatches, const double *host) { check(te_vec_upload_patches(v, first_patch, npatches, host)); }
+	void download(int first_patch, int npatches, double *host) const { check(te_vec_download_patches(v, first_patch, npatches, host)); }
+};
+
+/// G = grad u with the ghosts te_apply uses; bdata: a boundary vector (te_vec_create_boundary) or NULL. Collective.
+template <size_t D> void gradient(std::shared_ptr<const Vector<D>> u, HipFaceVector<D> &G, const te_vec *bdata = nullptr)
+{
+	check(te_gradient(G.ctx->g, G.level, HipVector<D>::raw(u), bdata, G.raw()));
+}
+/// out = alpha div U (patch-local)
+template <size_t D> void divergence(const HipFaceVector<D> &U, std::shared_ptr<Vector<D>> out, double alpha = 1.0)
+{
+	check(te_divergence(U.ctx->g, U.level, alpha, U.raw(), const_cast<te_vec *>(HipVector<D>::raw(out))));
+}
+/// U -= alpha grad p in one pass. Collective.
+template <size_t D> void project(HipFaceVector<D> &U, std::shared_ptr<const Vector<D>> p, double alpha = 1.0, const te_vec *bdata = nullptr)
+{
+	check(te_project(U.ctx->g, U.level, alpha, HipVector<D>::raw(p), bdata, U.raw()));
+}
 } // namespace tehip
 #endif
