@@ -236,6 +236,30 @@ int te_smooth(te_gmg *g, int level, const te_vec *f, te_vec *u, int smoother, do
 int te_restrict(te_gmg *g, int fine_level, const te_vec *fine, te_vec *coarse);
 /* GMG::Interpolator<D>::interpolate(coarse, fine) (GMG/Interpolator.h:39) == DrctIntp.h:80-113 */
 int te_prolong_add(te_gmg *g, int fine_level, const te_vec *coarse, te_vec *fine);
+/* The interpolator of a cycle. DIRECT copies the coarse cell's value to its fine cells (order 1); LINEAR is tri-/bilinear (order 2:
+ * with AvgRstr the orders add up to more than the operator's 2, and the cycle's convergence factor no longer grows with the depth of
+ * the hierarchy). LINEAR stands behind GMG/TriLinIntp.h (which the reference's build leaves out), restated so that it stays
+ * patch-local plus face ghosts. E = the coarse patch's values extended to indices -1 .. n per axis: with ONE axis out of range the
+ * ghost te_apply's stencil reads there for homogeneous boundary data (the neighbour's cell; 2 gamma - m on a coarse/fine face, gamma
+ * the interface value of SchurHelper::interpolateToInterface and m the cell just inside; -m on a physical Dirichlet face, +m on a
+ * Neumann face); with k >= 2 axes out of range (patch edges and corners), m = the patch's own cell with those indices clamped, the
+ * sum over the out-of-range axes, in ascending order, of the face ghost of m through that axis, minus (k - 1) m -- no edge or corner
+ * neighbour is read. Fine cell i of a child in orthant o takes, per axis a, c = (i + o_a n) >> 1 and d = -1 (i even) / +1 (i odd),
+ * and v <- 0.75 E[c] + 0.25 E[c + d], x then y then z (27/9/9/9/3/3/3/1 over 64 in 3D, 9/3/3/1 over 16 in 2D); fine += v. A patch
+ * that copies through (orthant -1) receives fine += coarse as in DrctIntp. */
+#define TE_INTERP_DIRECT 0 /* GMG/DrctIntp.h:80-113 (the default) */
+#define TE_INTERP_LINEAR 1 /* stands behind GMG/TriLinIntp.h, restated as above */
+/* GMG::Interpolator<D>::interpolate(coarse, fine) with TE_INTERP_LINEAR: the arguments and checks of te_prolong_add. Makes the COARSE
+ * level's ghosts current as te_apply does. Single rank: TE_ESTATE on a sharded hierarchy -- the sharded form is future work (the ring
+ * of the parent's block for children on another rank, and the proof of bit-identity with the single-rank run, are missing). */
+int te_prolong_linear_add(te_gmg *g, int fine_level, const te_vec *coarse, te_vec *fine);
+/* Which prolongation te_vcycle, and through it te_bicgstab, uses (te_cycle_opts keeps its layout). With LINEAR the cycle prolongs
+ * with te_prolong_linear_add's kernel on the stored iterate and runs plain post-sweeps: every fused form that has DrctIntp's
+ * arithmetic in it (the sweeps on u + P e, the unstored iterate of fuse = 3 and what hangs on it) is off, the restriction-side
+ * fusions stay; fuse = 1 is bit-identical to 0 and 3 to 2. With DIRECT -- never set, or set back -- nothing changes. TE_EINVAL for
+ * an unknown kind; TE_ESTATE for LINEAR on a sharded hierarchy (as above; DIRECT is untouched there). */
+int te_gmg_set_interpolator(te_gmg *g, int kind);
+int te_gmg_interpolator(const te_gmg *g);
 /* GMG::Cycle<D>::apply(f, u) (GMG/Cycle.h:116-126) on level 0 */
 int te_vcycle(te_gmg *g, const te_cycle_opts *o, const te_vec *f, te_vec *u);
 /* BiCGStab<D>::solve(vg, A, x, b, Mr, max_it, tol) (BiCGStab.h:45-106). Mr = te_vcycle when

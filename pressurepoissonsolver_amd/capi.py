@@ -30,6 +30,7 @@ TE_OK, TE_EINVAL, TE_EHIP, TE_ESTATE, TE_EIO, TE_EUNSUPPORTED, TE_ENOMEM = 0, -1
 SMOOTH_PATCH_SOLVE, SMOOTH_JACOBI, SMOOTH_RBGS, SMOOTH_PATCH_BCGS = 0, 1, 2, 3
 PROBLEM_TRIG, PROBLEM_GAUSS, PROBLEM_RANDOM = 0, 1, 2
 SCHUR_PREC_NONE, SCHUR_PREC_CHEB = 0, 1
+INTERP_DIRECT, INTERP_LINEAR = 0, 1  # TE_INTERP_*: DrctIntp (the default), tri-/bilinear
 
 
 class CycleOpts(C.Structure):
@@ -119,6 +120,9 @@ SYMBOLS = {
     "te_smooth": (_I, [_P, _I, _P, _P, _I, _D, _I]),
     "te_restrict": (_I, [_P, _I, _P, _P]),
     "te_prolong_add": (_I, [_P, _I, _P, _P]),
+    "te_prolong_linear_add": (_I, [_P, _I, _P, _P]),
+    "te_gmg_set_interpolator": (_I, [_P, _I]),
+    "te_gmg_interpolator": (_I, [_P]),
     "te_vcycle": (_I, [_P, C.POINTER(CycleOpts), _P, _P]),
     "te_bicgstab": (_I, [_P, C.POINTER(CycleOpts), _P, _P, _I, _D, C.POINTER(_I), _PD]),
     "te_gmg_release_workspace": (_I, [_P]),
@@ -638,6 +642,21 @@ class GMG:
 
     def restrict(self, coarse, fine, fine_level=0): check(lib().te_restrict(self.h, fine_level, fine.h, coarse.h))
     def interpolate(self, coarse, fine, fine_level=0): check(lib().te_prolong_add(self.h, fine_level, coarse.h, fine.h))
+    def interpolate_linear(self, coarse, fine, fine_level=0):
+        """Interpolator::interpolate with the tri-/bilinear interpolator (TE_INTERP_LINEAR), whatever the solver's setting"""
+        check(lib().te_prolong_linear_add(self.h, fine_level, coarse.h, fine.h))
+
+    def set_interpolator(self, kind):
+        """which prolongation cycle() and bicgstab() use: INTERP_DIRECT (default) or INTERP_LINEAR"""
+        check(lib().te_gmg_set_interpolator(self.h, int(kind)))
+
+    @property
+    def interpolator(self):
+        kind = lib().te_gmg_interpolator(self.h)
+        if kind < 0:
+            check(kind)
+        return kind
+
     def cycle(self, opts, f, u): check(lib().te_vcycle(self.h, C.byref(opts), f.h, u.h))
 
     def bicgstab(self, x, b, opts=None, max_it=1000, tol=1e-12):

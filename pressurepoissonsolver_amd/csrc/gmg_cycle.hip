@@ -46,6 +46,11 @@ int visit(te_gmg *g, const te_cycle_opts *o, int l, const te_vec *f, te_vec *u, 
 	LevelHost &L        = *g->levels[l];
 	int        rc;
 	g->cur_level        = l;
+	// The one predicate for every fused form below that has DrctIntp's arithmetic baked in: the sweeps on u + P e (pending_prolong),
+	// the unstored iterate of fuse = 3 with the ghost terms exported for it (fcorr) and the pre-sweep that keeps only face layers
+	// (ps_faces_req), the 2D folds. With the linear interpolator they are off: the iterate is stored, te_prolong_linear_add's kernel
+	// prolongs, plain post-sweeps follow. The restriction-side fusions do not depend on the interpolator and stay.
+	const bool drct = g->interp == TE_INTERP_DIRECT;
 	const double *fcorr_in = (L.f_has_corr && L.fcorr.p) ? L.fcorr.p : nullptr; // ghost terms that still belong to f (see below)
 	L.f_has_corr           = false;
 	const Fold2DHost fold_in = L.fold_pending; // (2D) ghost terms this level's pre-sweep kernel still has to add to f itself
@@ -156,7 +161,7 @@ int visit(te_gmg *g, const te_cycle_opts *o, int l, const te_vec *f, te_vec *u, 
         g->cur_level = l;
         // prepFiner (Cycle.h:74-80). When the very next step is an RB-GS sweep on a level without ghost
         // slots, that sweep reads u + P(coarse u) on the fly instead (same bits, one HBM pass less).
-        if (o->fuse && next_sweeps > 0
+        if (drct && o->fuse && next_sweeps > 0
             && (L.prolong_fusable || L.prolong_fusable_cf)
             && (o->smoother == TE_SMOOTH_RBGS
                 || (o->smoother == TE_SMOOTH_PATCH_SOLVE && L.dim == 3 && !g->cfg.has(O_PS_SLOW))
@@ -165,6 +170,7 @@ int visit(te_gmg *g, const te_cycle_opts *o, int l, const te_vec *f, te_vec *u, 
             return TE_OK;
         }
         L.xf_valid_for = nullptr; // u changes in place
+        if (!drct) return doProlongLinear(g, l, C.u->d, u->d);
         return doProlong(g, l, C.u->d, u->d);
 	};
 	// opts.fuse = 2: one pre-smoothing RB-GS sweep from the zero iterate, the residual and its restriction in one
@@ -174,7 +180,7 @@ int visit(te_gmg *g, const te_cycle_opts *o, int l, const te_vec *f, te_vec *u, 
 	// (a level takes the fuse = 3 path when ...; the same predicate for the next level decides whether that level can
 	// read its right-hand side together with exported ghost terms, see below)
 	auto unstoredAt = [&](LevelHost &LL, bool has_coarser) {
-		return o->fuse >= 3 && o->pre_sweeps == 1 && o->smoother == TE_SMOOTH_RBGS && LL.fuse2_ok && has_coarser && o->cycle_type == 0
+		return drct && o->fuse >= 3 && o->pre_sweeps == 1 && o->smoother == TE_SMOOTH_RBGS && LL.fuse2_ok && has_coarser && o->cycle_type == 0
 		       && o->post_sweeps >= 1 && (LL.prolong_fusable || (LL.dim == 3 && LL.prolong_fusable_cf && !g->cfg.has(O_NO_FUSE3_CF))) && LL.n >= 4
 		       && !g->cfg.has(O_NO_FUSE2) && !g->cfg.has(O_NO_FUSE3);
 	};
@@ -196,7 +202,7 @@ int visit(te_gmg *g, const te_cycle_opts *o, int l, const te_vec *f, te_vec *u, 
 		// kernel adds the ghost terms of the restricted residual to its right-hand side before reading it, and the fix-up launch
 		// of this level does not happen (bit-identical: the same additions in the same order; rank-local: every child of a local
 		// coarse patch is local, no block travels)
-		const bool fold_out = L.dim == 2 && l + 2 < nl && C.fuse2_ok && L.n >= 4 && L.n <= 64 && L.tx_up.empty() && L.n_down == 0 && !L.repl_up
+		const bool fold_out = drct && L.dim == 2 && l + 2 < nl && C.fuse2_ok && L.n >= 4 && L.n <= 64 && L.tx_up.empty() && L.n_down == 0 && !L.repl_up
 		                      && L.child.p && L.Pc == C.P && !g->cfg.has(O_2D_NO_FOLD);
 		// (the kernel variants that form a pending right-hand side exist for the 3D path that does not store the iterate)
 		const PendingRhs *fs = (pend && u_unstored && L.dim == 3 && !fcorr_in && L.P > 0 && !g->recording) ? pend : nullptr;
@@ -222,7 +228,7 @@ int visit(te_gmg *g, const te_cycle_opts *o, int l, const te_vec *f, te_vec *u, 
 		u_zero = false;
 		// opts.fuse = 3: ... and so does everything the post-sweep reads of this iterate (its interface terms, k_face_corr3d
 		// on u + P e): the pre-sweep stores the six face layers of its result and nothing else (bit-identical; rank-local)
-		L.ps_faces_req = o->fuse >= 3 && o->cycle_type == 0 && o->post_sweeps >= 1 && L.n == 32 && L.P_global >= 256 && L.prolong_fusable
+		L.ps_faces_req = drct && o->fuse >= 3 && o->cycle_type == 0 && o->post_sweeps >= 1 && L.n == 32 && L.P_global >= 256 && L.prolong_fusable
 		                 && (L.sym_ok || L.n_pure == L.P) && L.f6buf.p && !g->cfg.has(O_PS_SLOW) && !g->cfg.has(O_PS_MODE)
 		                 && !g->cfg.has(O_NO_PS_FACES);
 		if ((rc = smoothOnce(g, l, f, u, TE_SMOOTH_PATCH_SOLVE, o->omega, true))) return rc;

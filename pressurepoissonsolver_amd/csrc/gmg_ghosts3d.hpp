@@ -129,6 +129,17 @@ template <int N, class F> int withGhosts(te_gmg *g, LevelHost &L, const double *
 	return TE_OK;
 }
 
+// z-slabs per patch on levels with few patches: the rule of launchStencilN (the MAC operators, the linear prolongation)
+template <int N> inline int projSlabs(const te_gmg *g, int P)
+{
+	int zs = 1;
+	if (N >= 8) {
+		while (zs < 4 && (g->cfg.has(O_ZS_FORCE) || (size_t) P * zs < 2048) && N / (zs * 2) >= 4) zs *= 2;
+		if (zs == 4 && N == 32 && P <= 64 && !g->cfg.has(O_NO_ZS8)) zs = 8;
+	}
+	return zs;
+}
+
 // The restricted blocks of this rank's patches to the other ranks (the kernels before this have written them into the local
 // coarse patches or into upbuf), the other ranks' blocks into the local coarse patches. repl_up (the coarse level lives on
 // every rank): the finished octants are copied out of the coarse patches first -- one copy, sent to everybody.

@@ -10,6 +10,7 @@
 //   gmg_krylov.hip     Vector<D> BLAS-1 entries and te_bicgstab (BiCGStab.h:45-106)
 //   gmg_bc.hip         boundary vectors, the fold of boundary data into a right-hand side, Init with a kind per side (bckernels.hpp)
 //   gmg_projection.hip face vectors, MAC gradient, divergence, pressure projection (projkernels.hpp)
+//   gmg_prolong.hip    the linear interpolator and the solver's choice of interpolator (prolongkernels.hpp)
 #pragma once
 #include "capi_common.hpp"
 #include "level_tables.hpp"
@@ -82,7 +83,9 @@ enum KClass : int {
 	// right-hand side and a read + write of the patch (24 B/site) whatever the iteration count
 	KC_PATCH_BCGS,
 	// the MAC operators of projkernels.hpp (34.25 / 32.75 / 59 B per site at 32^3 patches)
-	KC_GRADIENT, KC_DIVERGENCE, KC_PROJECT, KC_COUNT
+	KC_GRADIENT, KC_DIVERGENCE, KC_PROJECT,
+	// the linear interpolator (prolongkernels.hpp): 16 + 1 B per fine site plus halos, the class of KC_PROLONG's 17
+	KC_PROLONG_LINEAR, KC_COUNT
 };
 extern const char *kclassName[KC_COUNT]; // (gmg_core.hip)
 
@@ -389,6 +392,7 @@ struct te_gmg {
 	// bytes per plane and side instead of 8 of every 128-byte line of the neighbour patch: 1.24 x -> 1.0x of its algorithmic bytes)
 	bool        keep_final_xf = false;
 	int                                     dim = 3, n = 0;
+	int                                     interp = TE_INTERP_DIRECT; // the prolongation of te_vcycle (te_gmg_set_interpolator)
 	std::vector<std::unique_ptr<LevelHost>> levels;
 	DevBuf<double>                          partial, result;
 	DevBuf<double>                          loopbuf; // TE_RCCL_LOOPBACK (diagnostic): source and sink of the self-addressed messages
@@ -691,6 +695,8 @@ int patchSolve(te_gmg *g, LevelHost &L, const double *f, double *u, bool zero_gu
                bool *swapped = nullptr);
 int doRestrict(te_gmg *g, int fine_level, const double *fine, double *coarse);
 int doProlong(te_gmg *g, int fine_level, const double *coarse, double *fine);
+// ---- gmg_prolong.hip
+int doProlongLinear(te_gmg *g, int fine_level, const double *coarse, double *fine);
 // ---- gmg_launch2d.hip
 int prepareGhosts2d(te_gmg *g, LevelHost &L, const double *u);
 template <int MODE> int launchStencil2d(te_gmg *g, LevelHost &L, const double *u, const double *f, double *out, double omega, int redmode = RED_NONE,

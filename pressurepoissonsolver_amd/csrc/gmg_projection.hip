@@ -28,17 +28,6 @@ static int faceGeom(LevelHost &L, const te_vec *bdata, FaceGeom *F)
 	return TE_OK;
 }
 
-// z-slabs per patch on levels with few patches: the rule of launchStencilN
-template <int N> static int projSlabs(const te_gmg *g, int P)
-{
-	int zs = 1;
-	if (N >= 8) {
-		while (zs < 4 && (g->cfg.has(O_ZS_FORCE) || (size_t) P * zs < 2048) && N / (zs * 2) >= 4) zs *= 2;
-		if (zs == 4 && N == 32 && P <= 64 && !g->cfg.has(O_NO_ZS8)) zs = 8;
-	}
-	return zs;
-}
-
 template <int N, bool PROJECT> static int gradientN(te_gmg *g, LevelHost &L, const FaceGeom &F, const double *u, double *G, double alpha)
 {
 	const int zs     = projSlabs<N>(g, L.P);

@@ -9,6 +9,7 @@
 //   HipSmoother<D>     : GMG::Smoother<D>     (GMG/Smoother.h:39)            == FFTBlockJacobiSmoother (kind 0)
 //   HipRestrictor<D>   : GMG::Restrictor<D>   (GMG/Restrictor.h:39-40)       == AvgRstr
 //   HipInterpolator<D> : GMG::Interpolator<D> (GMG/Interpolator.h:39-40)     == DrctIntp
+//   HipLinearInterpolator<D> : GMG::Interpolator<D>                            stands behind TriLinIntp (te_prolong_linear_add; single rank)
 //   HipCycle<D>        : Operator<D>          whole GMG::Cycle<D>::apply (GMG/Cycle.h:116-126) in one call
 // The Schur-complement route (--schur, apps/3d/steady.cpp:336-420, apps/2d/steady.cpp:383-480; single rank):
 //   HipSchurVG<D>      : VectorGenerator<D-1> SchurHelper<D>::getNewSchurVec (SchurHelper.h:156-160): HipVector<D-1> over
@@ -267,7 +268,23 @@ template <size_t D> class HipInterpolator : public GMG::Interpolator<D>
 	}
 };
 
-/// The whole preconditioner M = GMG cycle in one native call (what CycleFactory3d::getCycle returns).
+/// The tri-/bilinear interpolator (TE_INTERP_LINEAR, include/te_hip.h): what GMG/TriLinIntp.h was written for, patch-local plus
+/// face ghosts. Single rank: on a sharded hierarchy interpolate() throws (TE_ESTATE).
+template <size_t D> class HipLinearInterpolator : public GMG::Interpolator<D>
+{
+	std::shared_ptr<Context> ctx;
+	int                      fine_level;
+
+	public:
+	HipLinearInterpolator(std::shared_ptr<Context> ctx_, int fine_level_) : ctx(ctx_), fine_level(fine_level_) {}
+	void interpolate(std::shared_ptr<const Vector<D>> coarse, std::shared_ptr<Vector<D>> fine) const override
+	{
+		check(te_prolong_linear_add(ctx->g, fine_level, HipVector<D>::raw(coarse), const_cast<te_vec *>(HipVector<D>::raw(fine))));
+	}
+};
+
+/// The whole preconditioner M = GMG cycle in one native call (what CycleFactory3d::getCycle returns). It prolongs with the
+/// solver's interpolator (te_gmg_set_interpolator; TE_INTERP_DIRECT unless set): the second constructor sets it first.
 template <size_t D> class HipCycle : public Operator<D>
 {
 	std::shared_ptr<Context> ctx;
@@ -275,6 +292,11 @@ template <size_t D> class HipCycle : public Operator<D>
 
 	public:
 	HipCycle(std::shared_ptr<Context> ctx_, const te_cycle_opts &o) : ctx(ctx_), opts(o) {}
+	HipCycle(std::shared_ptr<Context> ctx_, const te_cycle_opts &o, int interpolator) : ctx(ctx_), opts(o)
+	{
+		check(te_gmg_set_interpolator(ctx->g, interpolator));
+	}
+	int interpolator() const { return te_gmg_interpolator(ctx->g); }
 	void apply(std::shared_ptr<const Vector<D>> f, std::shared_ptr<Vector<D>> u) const override
 	{
 		check(te_vcycle(ctx->g, &opts, HipVector<D>::raw(f), const_cast<te_vec *>(HipVector<D>::raw(u))));
