@@ -274,6 +274,35 @@ int te_bicgstab(te_gmg *g, const te_cycle_opts *o, te_vec *x, const te_vec *b, i
  * caller that has finished solving and wants the memory back (the next te_bicgstab allocates them again). */
 int te_gmg_release_workspace(te_gmg *g);
 
+/* The FMG interpolation: fine = Pi coarse. It SETS fine (it does not add), and it interpolates a SOLUTION, which carries boundary
+ * data, so it reads none. The rule is TE_INTERP_LINEAR's with two changes. (1) In the extended block E, the ghost through a PHYSICAL
+ * face, Dirichlet or Neumann alike, is the quadratic extrapolation 3 m - 3 m1 + m2 of the first, second and third cells inside along
+ * that axis (n >= 4: they exist); faces with a neighbour keep the ghost te_apply reads (the neighbour's cell, 2 gamma - m on a
+ * coarse/fine face), edges and corners the rule "sum of the face ghosts of the clamped cell, ascending axes, minus (k - 1) m".
+ * (2) Per axis a, with c = (i + o_a n) >> 1 and d = -1 (i even) / +1 (i odd): v <- (30 E[c] + 5 E[c + d] - 3 E[c - d]) / 32, x then y
+ * then z. With the extrapolated ghost the centred formula is the one-sided quadratic through the three innermost cells, so quadratic
+ * polynomials are reproduced on every cell of a uniform hierarchy, the first and last layers included (order 3, above the operator's
+ * 2, as nested iteration needs). A patch that copies through (orthant -1) receives fine = coarse bit for bit. The arguments and
+ * checks of te_prolong_linear_add; makes the COARSE level's ghosts current as te_apply does; single rank (TE_ESTATE on a sharded
+ * hierarchy). */
+int te_prolong_quadratic(te_gmg *g, int fine_level, const te_vec *coarse, te_vec *fine);
+/* Full multigrid (nested iteration): a solution of A u = f + (boundary terms) to discretisation accuracy for about the cost of a
+ * few finest-level cycles, instead of te_bicgstab's solve to an algebraic tolerance. `f` is the INTERIOR right-hand side on level 0
+ * with NO boundary terms folded in (the caller does not call te_add_boundary_rhs first); `bdata` the level-0 boundary vector, or
+ * NULL for homogeneous data; `u` the result; cycles >= 0 the number of cycles per level (2 is enough with TE_INTERP_LINEAR and V(1,1);
+ * 1, or DIRECT with 2, is not in 3D); rel_resid (may be NULL) receives |F_0 - A u|_2 / |F_0|_2.
+ *   f_0 = f, b_0 = bdata; f_l+1 = te_restrict f_l, b_l+1 = te_boundary_restrict b_l; F_l = f_l + what te_add_boundary_rhs(b_l, .)
+ *   adds, on EVERY level (the restriction of a folded Dirichlet term is not the coarse level's: -2 g / h^2 averages to -4 g / h_c^2);
+ *   on the coarsest level, which must be ONE patch, U = the exact patch solve of F from zero (the TE_SMOOTH_PATCH_SOLVE sweep a
+ *   cycle runs there under exact_coarse); then for every finer level U_l = te_prolong_quadratic U_l+1 and, `cycles` times,
+ *   U_l += (one cycle with `o` and the solver's interpolator, entered at level l, on F_l - A_l U_l).
+ * The work vectors (three of level 0, four of every coarser level: 3 GiB + 1/7 at 512^3) are allocated at the first call and kept;
+ * te_gmg_release_workspace / te_gmg_destroy free them. The call leaves the solver's interpolator and options as they are, and a
+ * te_vcycle afterwards gives the bits it gave before. On an all-Neumann hierarchy the caller supplies compatible data, as for
+ * te_bicgstab, and the result is defined up to a constant. TE_EINVAL: vectors of the wrong kind, level or solver, cycles < 0;
+ * TE_ESTATE: a sharded hierarchy (single rank only), or a coarsest level of more than one patch (max_levels / patches_per_proc). */
+int te_fmg(te_gmg *g, const te_cycle_opts *o, const te_vec *f, const te_vec *bdata, te_vec *u, int cycles, double *rel_resid);
+
 /* The TE_* switches (docs/SWITCHES.md) are read from the environment once, in te_gmg_create. This call sets (value) or
  * clears (NULL) one of them for this solver afterwards -- how the tests pin one implementation against another. TE_ESTATE
  * for the few that shape the level tables and are therefore fixed at creation; TE_EINVAL for an unknown name. */
@@ -418,6 +447,14 @@ int te_add_boundary_rhs(te_gmg *g, int level, const te_vec *bdata, te_vec *f);
 /* the canned problems' boundary data (TE_PROBLEM_TRIG / TE_PROBLEM_GAUSS): the exact solution at the face points of Dirichlet faces,
  * its derivative along the axis on Neumann faces -- what te_init_problem_sides folds in */
 int te_boundary_sample(te_gmg *g, int level, int problem, te_vec *bdata);
+/* The boundary vector of the next coarser level: each entry of a coarse physical-face block is the mean of the 2^(dim-1) fine face
+ * entries that cover it -- 3D ((a + b) + (c + d)) * 0.25 with a, b adjacent along the face's lower remaining axis, 2D (a + b) * 0.5 --
+ * from the block of the child whose orthant bits on the face's remaining axes name that quadrant; a patch that copies through hands
+ * its blocks on bit for bit. Dirichlet values and Neumann derivatives restrict alike. fine_bdata: a boundary vector of fine_level,
+ * coarse_bdata: one of fine_level + 1 (TE_EINVAL otherwise). One writer per entry, deterministic. Single rank (TE_ESTATE on a
+ * sharded hierarchy). Folding the result with te_add_boundary_rhs gives the coarse level's boundary terms; restricting a FOLDED
+ * right-hand side does not (twice the Dirichlet term). */
+int te_boundary_restrict(te_gmg *g, int fine_level, const te_vec *fine_bdata, te_vec *coarse_bdata);
 /* te_init_problem with the kind of every physical face taken from the hierarchy's side mask (te_hier_build_bc) instead of one flag:
  * Init::initDirichlet's term on Dirichlet faces and Init::initNeumann's on Neumann faces in one pass (for mask 0 / all bits the
  * very bits of te_init_problem with neumann = 0 / 1). */

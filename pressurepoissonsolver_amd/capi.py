@@ -121,6 +121,9 @@ SYMBOLS = {
     "te_restrict": (_I, [_P, _I, _P, _P]),
     "te_prolong_add": (_I, [_P, _I, _P, _P]),
     "te_prolong_linear_add": (_I, [_P, _I, _P, _P]),
+    "te_prolong_quadratic": (_I, [_P, _I, _P, _P]),
+    "te_boundary_restrict": (_I, [_P, _I, _P, _P]),
+    "te_fmg": (_I, [_P, _P, _P, _P, _P, _I, _PD]),
     "te_gmg_set_interpolator": (_I, [_P, _I]),
     "te_gmg_interpolator": (_I, [_P]),
     "te_vcycle": (_I, [_P, C.POINTER(CycleOpts), _P, _P]),
@@ -619,7 +622,7 @@ class GMG:
         check(lib().te_gmg_set_option(self.h, name.encode(), None if value is None else str(value).encode()))
 
     def release_workspace(self):
-        """hand te_bicgstab's work vectors back (8 x a level-0 vector)"""
+        """hand te_bicgstab's work vectors (8 x a level-0 vector) and te_fmg's back"""
         check(lib().te_gmg_release_workspace(self.h))
 
     def set_allreduce(self, fn):
@@ -645,6 +648,21 @@ class GMG:
     def interpolate_linear(self, coarse, fine, fine_level=0):
         """Interpolator::interpolate with the tri-/bilinear interpolator (TE_INTERP_LINEAR), whatever the solver's setting"""
         check(lib().te_prolong_linear_add(self.h, fine_level, coarse.h, fine.h))
+
+    def interpolate_quadratic(self, coarse, fine, fine_level=0):
+        """the FMG interpolation te_prolong_quadratic: fine = Pi coarse (sets; reads no boundary data)"""
+        check(lib().te_prolong_quadratic(self.h, fine_level, coarse.h, fine.h))
+
+    def boundary_restrict(self, fine_bdata, coarse_bdata, fine_level=0):
+        """the boundary vector of level fine_level + 1: means of the 2^(dim-1) fine face entries that cover a coarse one"""
+        check(lib().te_boundary_restrict(self.h, fine_level, fine_bdata.h, coarse_bdata.h))
+
+    def fmg(self, f, u, opts, bdata=None, cycles=2):
+        """te_fmg: full multigrid from the INTERIOR right-hand side f and the level-0 boundary vector (None: homogeneous data),
+        `cycles` cycles per level with opts and the solver's interpolator -> the relative residual |F - A u| / |F|"""
+        rr = C.c_double()
+        check(lib().te_fmg(self.h, C.byref(opts), f.h, bdata.h if bdata is not None else None, u.h, int(cycles), C.byref(rr)))
+        return rr.value
 
     def set_interpolator(self, kind):
         """which prolongation cycle() and bicgstab() use: INTERP_DIRECT (default) or INTERP_LINEAR"""

@@ -114,6 +114,38 @@ template <int D> __global__ __launch_bounds__(256) void k_boundary_rhs(BcGeom G,
 	}
 }
 
+// te_boundary_restrict: the boundary vector of the next coarser level. Each entry of a coarse block is the mean of the 2^(D-1)
+// fine entries that cover it -- 3D ((a + b) + (c + d)) * 0.25 with a, b adjacent along the face's lower remaining axis, 2D
+// (a + b) * 0.5 --, taken from the block of the child in that quadrant (tab: level_tables.hpp brestrict); a patch that copies
+// through hands its block on bit for bit. One workgroup per COARSE block, one thread per entry: one writer, no atomics. Dirichlet
+// values and Neumann derivatives restrict alike. 8 B written + 8 * 2^(D-1) B read per coarse value.
+template <int D>
+__global__ __launch_bounds__(256) void k_boundary_restrict(int n, int ncb, const int32_t *__restrict__ tab, const double *__restrict__ fine,
+                                                            double *__restrict__ coarse)
+{
+	const int cb = blockIdx.x;
+	if (cb >= ncb) return;
+	const int32_t *row = tab + (size_t) cb * 5;
+	const int      h = n / 2, nf = D == 3 ? n * n : n;
+	double        *dst = coarse + (size_t) cb * nf;
+	if (row[0]) {
+		const double *src = fine + (size_t) row[1] * nf;
+		for (int j = threadIdx.x; j < nf; j += 256) dst[j] = src[j];
+		return;
+	}
+	for (int j = threadIdx.x; j < nf; j += 256) {
+		const int j0 = j % n, j1 = j / n; // (2D: j1 = 0)
+		const int u0 = j0 >= h, u1 = D == 3 && j1 >= h;
+		const double *src = fine + (size_t) row[1 + u0 + 2 * u1] * nf + 2 * (j0 - u0 * h);
+		if (D == 3) {
+			src += (size_t) n * 2 * (j1 - u1 * h);
+			dst[j] = ((src[0] + src[1]) + (src[n] + src[n + 1])) * 0.25;
+		} else {
+			dst[j] = (src[0] + src[1]) * 0.5;
+		}
+	}
+}
+
 // the canned problems' boundary data: the exact solution at the face point on a Dirichlet face, its derivative along the face's
 // axis on a Neumann face (what k_init3d / k_init2d fold in). One workgroup per (patch, side).
 template <int D, int PROB> __global__ __launch_bounds__(256) void k_boundary_sample(BcGeom G, double *__restrict__ bdata)

@@ -20,9 +20,39 @@ static int checkBoundaryVec(te_gmg *g, int level, const te_vec *v, const char *w
 		return te::fail(TE_EINVAL, std::string(who) + ": not a boundary vector of this level");
 	return TE_OK;
 }
+
+static const char *const kBrSharded = "te_boundary_restrict: on a sharded hierarchy the blocks of children on another rank would have to travel: not implemented";
+
+int doBoundaryRestrict(te_gmg *g, int fine_level, const double *fine_bdata, double *coarse_bdata)
+{
+	if (g->nranks > 1) return te::fail(TE_ESTATE, kBrSharded);
+	LevelHost &L = *g->levels[fine_level], &C = *g->levels[fine_level + 1];
+	if (C.nbf == 0) return TE_OK;
+	int rc;
+	if (!L.brestrict.p && (rc = L.brestrict.upload(L.brestrict_host))) return rc;
+	if (L.brestrict.n != (size_t) C.nbf * 5) return te::fail(TE_ESTATE, "te_boundary_restrict: the level has no restriction table");
+	Timed t(g, KC_BOUNDARY_RESTRICT, (size_t) C.nbf * C.nf);
+	if (L.dim == 3)
+		hipLaunchKernelGGL(k_boundary_restrict<3>, dim3(C.nbf), dim3(256), 0, g->stream, L.n, C.nbf, L.brestrict.p, fine_bdata, coarse_bdata);
+	else
+		hipLaunchKernelGGL(k_boundary_restrict<2>, dim3(C.nbf), dim3(256), 0, g->stream, L.n, C.nbf, L.brestrict.p, fine_bdata, coarse_bdata);
+	HIPCHK(hipGetLastError());
+	return TE_OK;
+}
 } // namespace tei
 
 extern "C" {
+int te_boundary_restrict(te_gmg *g, int fine_level, const te_vec *fine_bdata, te_vec *coarse_bdata)
+{
+	return guarded([&]() -> int {
+		int rc;
+		if ((rc = checkBoundaryVec(g, fine_level, fine_bdata, "te_boundary_restrict"))
+		    || (rc = checkBoundaryVec(g, fine_level + 1, coarse_bdata, "te_boundary_restrict")))
+			return rc;
+		return doBoundaryRestrict(g, fine_level, fine_bdata->d, coarse_bdata->d);
+	});
+}
+
 int te_vec_create_boundary(te_gmg *g, int level, te_vec **out)
 {
 	return guarded([&]() -> int {

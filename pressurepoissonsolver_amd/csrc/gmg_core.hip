@@ -9,7 +9,7 @@ const char *kclassName[KC_COUNT] = {"stencil_apply", "stencil_resid", "stencil_j
                                     "stencil_rbgs_slabs", "stencil_slabs", "patch_solve_3pass", "rbgs_zero_resid_restrict",
                                     "restrict_fixup", "rbgs_resweep_prolong", "rbgs_zero_resid_restrict_faces",
                                     "rbgs_resweep_prolong_fcorr", "rbgs_zero_resid_restrict_faces_fcorr", "fcorr_gather", "patch_solve_mfma_faces",
-                                    "bicg_update", "bicg_s", "bicg_p", "stencil_apply_dot", "patch_bcgs", "gradient", "divergence", "project", "prolong_linear"};
+                                    "bicg_update", "bicg_s", "bicg_p", "stencil_apply_dot", "patch_bcgs", "gradient", "divergence", "project", "prolong_linear", "prolong_quadratic", "boundary_restrict"};
 const char *optName[O_COUNT] = {"TE_2D_SIMPLE", "TE_2D_NO_MFMA", "TE_2D_NO_PF", "TE_2D_NO_MR_FUSE", "TE_2D_TPB", "TE_NO_FUSE2", "TE_NO_FUSE3",
                                 "TE_NO_FUSE3_CF", "TE_NO_CFP", "TE_NO_XF", "TE_NO_FCORR", "TE_NO_FCORR_CF", "TE_NO_GTAB", "TE_NO_OVERLAP",
                                 "TE_OVERLAP_MIN", "TE_NO_PS_FACES", "TE_PS_MODE", "TE_PS_SLOW", "TE_RBGS_NOSLAB", "TE_ZS_FORCE", "TE_NO_ZS8",
@@ -54,7 +54,7 @@ int buildLevel(te_gmg *g, const Hierarchy &H, int li)
 	L->dim = T.dim, L->n = T.n, L->P = T.P, L->P_global = T.P_global, L->nc = T.nc, L->nf = T.nf;
 	L->replicated = T.replicated, L->gathered = T.gathered;
 	L->nif = T.nif, L->if_own = std::move(T.if_own), L->if_start = std::move(T.if_start), L->if_contrib = std::move(T.if_contrib);
-	L->nbf = T.nbf, L->bface_host = std::move(T.bface);
+	L->nbf = T.nbf, L->bface_host = std::move(T.bface), L->brestrict_host = std::move(T.brestrict);
 	L->fx = std::move(T.fx), L->nremote = T.nremote;
 	L->nslots = T.nslots, L->ncf = T.ncf, L->n_int = T.n_int, L->n_bnd = T.n_bnd;
 	L->lds2d = T.lds2d, L->fuse2d = T.fuse2d, L->fuse2_ok = T.fuse2_ok;
@@ -244,6 +244,7 @@ void te_gmg_destroy(te_gmg *g)
 	}
 	for (te_vec *v : g->bicg_work)
 		if (v) te_vec_destroy(v);
+	fmgFree(g);
 	schurFree(g);
 	for (auto &e : g->ev_pool) {
 		(void) hipEventDestroy(e.a);
@@ -552,8 +553,8 @@ int te_stamps_read(te_gmg *g, unsigned long long *out, char (*names)[64], int *w
 }
 #endif
 
-// te_bicgstab keeps its eight level-0 work vectors between solves (8 GiB at 512^3); a caller that is done solving hands
-// them back with this call (they are allocated again by the next te_bicgstab)
+// te_bicgstab keeps its eight level-0 work vectors between solves (8 GiB at 512^3), te_fmg its own (three of level 0 and four of
+// every coarser level); a caller that is done solving hands them back with this call (the next solve allocates them again)
 int te_gmg_release_workspace(te_gmg *g)
 {
 	return guarded([&]() -> int {
@@ -562,6 +563,7 @@ int te_gmg_release_workspace(te_gmg *g)
 				if (v) te_vec_destroy(v);
 				v = nullptr;
 			}
+			fmgFree(g);
 			return TE_OK;
 	});
 }

@@ -415,6 +415,22 @@ int vcycleWith(te_gmg *g, const te_cycle_opts *o, const te_vec *f, te_vec *u, co
 	}
 }
 
+// One cycle entered at level l on the right-hand side f, result in u (te_fmg): what vcycleWith does around visit() without the
+// parts that belong to level 0 and to te_bicgstab (pending_rhs, keep_final_xf). f and u are vectors of level l that are not the
+// level's own; the levels' f / u / r / t from l down are the cycle's.
+int cycleFrom(te_gmg *g, const te_cycle_opts *o, int l, const te_vec *f, te_vec *u)
+{
+	int rc;
+	if (!o->fuse && (rc = te_vec_set(u, 0.0))) return rc; // Cycle.h:118
+	for (auto &L : g->levels) L->xf_valid_for = nullptr, L->ps_faces = L->ps_faces_req = false;
+	g->in_cycle = !g->cfg.has(O_NO_XF);
+	rc          = visit(g, o, l, f, u, o->fuse != 0);
+	g->in_cycle = false;
+	for (auto &L : g->levels) L->xf_valid_for = nullptr, L->ps_faces = L->ps_faces_req = false;
+	g->cur_level = 0;
+	return rc;
+}
+
 } // namespace tei
 
 extern "C" {

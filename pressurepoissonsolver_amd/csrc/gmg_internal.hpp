@@ -10,7 +10,8 @@
 //   gmg_krylov.hip     Vector<D> BLAS-1 entries and te_bicgstab (BiCGStab.h:45-106)
 //   gmg_bc.hip         boundary vectors, the fold of boundary data into a right-hand side, Init with a kind per side (bckernels.hpp)
 //   gmg_projection.hip face vectors, MAC gradient, divergence, pressure projection (projkernels.hpp)
-//   gmg_prolong.hip    the linear interpolator and the solver's choice of interpolator (prolongkernels.hpp)
+//   gmg_prolong.hip    the linear interpolator, the solver's choice of interpolator, the quadratic FMG interpolation (prolongkernels.hpp)
+//   gmg_fmg.hip        the full-multigrid solve te_fmg and its work vectors
 #pragma once
 #include "capi_common.hpp"
 #include "level_tables.hpp"
@@ -85,7 +86,10 @@ enum KClass : int {
 	// the MAC operators of projkernels.hpp (34.25 / 32.75 / 59 B per site at 32^3 patches)
 	KC_GRADIENT, KC_DIVERGENCE, KC_PROJECT,
 	// the linear interpolator (prolongkernels.hpp): 16 + 1 B per fine site plus halos, the class of KC_PROLONG's 17
-	KC_PROLONG_LINEAR, KC_COUNT
+	KC_PROLONG_LINEAR,
+	// te_fmg's own kernels: the quadratic FMG interpolation (8 + 1 B per fine site plus halos; cells = fine sites) and the
+	// restriction of a boundary vector (cells = coarse boundary values)
+	KC_PROLONG_QUADRATIC, KC_BOUNDARY_RESTRICT, KC_COUNT
 };
 extern const char *kclassName[KC_COUNT]; // (gmg_core.hip)
 
@@ -239,6 +243,9 @@ struct LevelHost {
 	int                  nbf = 0;
 	std::vector<int32_t> bface_host; // [P][2 dim], -1 on a face with a neighbour
 	DevBuf<int32_t>      bface;
+	// te_boundary_restrict from this level to the next (level_tables.hpp brestrict): host copy, uploaded at its first use
+	std::vector<int32_t> brestrict_host;
+	DevBuf<int32_t>      brestrict;
 
 	Level2D dev2() const
 	{
@@ -407,6 +414,7 @@ struct te_gmg {
 	void                                   *allreduce_user = nullptr;
 	// schedule check (te_gmg_verify_schedule): exchanges are recorded instead of performed
 	te_vec *bicg_work[8] = {nullptr}; // te_bicgstab's work vectors (level 0), allocated at its first call
+	struct FmgWs   *fmg   = nullptr;  // te_fmg's work vectors (gmg_fmg.hip), made at its first call
 	struct SchurWs *schur = nullptr;  // the Schur route's device tables and work vectors (gmg_schur.hip), made at its first use
 	const PendingRhs *pending_rhs = nullptr; // set by te_bicgstab around a cycle: level 0's right-hand side is still to be formed
 	bool recording = false;
@@ -697,6 +705,11 @@ int doRestrict(te_gmg *g, int fine_level, const double *fine, double *coarse);
 int doProlong(te_gmg *g, int fine_level, const double *coarse, double *fine);
 // ---- gmg_prolong.hip
 int doProlongLinear(te_gmg *g, int fine_level, const double *coarse, double *fine);
+int doProlongQuadratic(te_gmg *g, int fine_level, const double *coarse, double *fine);
+// ---- gmg_bc.hip
+int doBoundaryRestrict(te_gmg *g, int fine_level, const double *fine_bdata, double *coarse_bdata);
+// ---- gmg_fmg.hip
+void fmgFree(te_gmg *g); // (te_gmg_release_workspace, te_gmg_destroy)
 // ---- gmg_launch2d.hip
 int prepareGhosts2d(te_gmg *g, LevelHost &L, const double *u);
 template <int MODE> int launchStencil2d(te_gmg *g, LevelHost &L, const double *u, const double *f, double *out, double omega, int redmode = RED_NONE,
@@ -723,6 +736,7 @@ void schurFree(te_gmg *g); // (te_gmg_destroy)
 // ---- gmg_cycle.hip
 int visit(te_gmg *g, const te_cycle_opts *o, int l, const te_vec *f, te_vec *u, bool u_zero);
 int vcycleWith(te_gmg *g, const te_cycle_opts *o, const te_vec *f, te_vec *u, const PendingRhs *pending); // te_vcycle; `pending`: see PendingRhs
+int cycleFrom(te_gmg *g, const te_cycle_opts *o, int l, const te_vec *f, te_vec *u); // one cycle entered at level l (te_fmg)
 
 // x-face columns of `d`, if the level still holds them (RB-GS sweeps and the single-pass patch solve produce them, inside te_vcycle)
 inline const double *xfFor(LevelHost &L, const double *d) { return (d && L.xf_valid_for == d) ? L.xfbuf[L.xf_cur].p : nullptr; }

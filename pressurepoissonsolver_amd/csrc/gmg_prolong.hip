@@ -1,5 +1,5 @@
-// The linear interpolator (prolongkernels.hpp; see gmg_internal.hpp): its launches, te_prolong_linear_add, and the solver's choice
-// of interpolator (te_gmg_set_interpolator). The prolongation reads the COARSE level's ghosts, made current exactly as te_apply
+// The linear interpolator (prolongkernels.hpp; see gmg_internal.hpp): its launches, te_prolong_linear_add, the solver's choice
+// of interpolator (te_gmg_set_interpolator), and the quadratic FMG interpolation te_prolong_quadratic. The prolongation reads the COARSE level's ghosts, made current exactly as te_apply
 // makes them (withGhosts / prepareGhosts2d). Single rank: on a sharded hierarchy the parent's ring block of a child on another
 // rank would have to travel, and the bit-identity with the single-rank run would have to be shown first.
 #include "gmg_ghosts3d.hpp"
@@ -59,9 +59,70 @@ int doProlongLinear(te_gmg *g, int fine_level, const double *coarse, double *fin
 		default: return prolongLinearN<32>(g, L, C, coarse, fine);
 	}
 }
+
+// ---- the quadratic FMG interpolation (te_prolong_quadratic): fine = Pi coarse
+template <int N> static int prolongQuadraticN(te_gmg *g, LevelHost &L, LevelHost &C, const double *coarse, double *fine)
+{
+	const int zs     = projSlabs<N>(g, L.P);
+	auto      launch = [&](LevelDev D) {
+        Timed      t(g, KC_PROLONG_QUADRATIC, (size_t) L.P * L.nc);
+        const dim3 grid(8 * ((L.P * zs + 7) / 8)), blk(Tile3<N>::TPB);
+        switch (zs) {
+            case 1: hipLaunchKernelGGL((k_prolong_quadratic3d<N, 1>), grid, blk, 0, g->stream, L.P, D, L.parent.p, L.orth.p, coarse, fine); break;
+            case 2:
+                if constexpr (N >= 8) hipLaunchKernelGGL((k_prolong_quadratic3d<N, 2>), grid, blk, 0, g->stream, L.P, D, L.parent.p, L.orth.p, coarse, fine);
+                break;
+            case 8:
+                if constexpr (N >= 32) hipLaunchKernelGGL((k_prolong_quadratic3d<N, 8>), grid, blk, 0, g->stream, L.P, D, L.parent.p, L.orth.p, coarse, fine);
+                break;
+            default:
+                if constexpr (N >= 16) hipLaunchKernelGGL((k_prolong_quadratic3d<N, 4>), grid, blk, 0, g->stream, L.P, D, L.parent.p, L.orth.p, coarse, fine);
+                break;
+        }
+	};
+	int rc = withGhosts<N>(g, C, coarse, launch);
+	if (rc) return rc;
+	HIPCHK(hipGetLastError());
+	return TE_OK;
+}
+
+int doProlongQuadratic(te_gmg *g, int fine_level, const double *coarse, double *fine)
+{
+	if (g->nranks > 1)
+		return te::fail(TE_ESTATE, "te_prolong_quadratic: not implemented on a sharded hierarchy (the ring of the parent's block for children on another rank is missing)");
+	LevelHost &L = *g->levels[fine_level], &C = *g->levels[fine_level + 1];
+	if (L.P == 0) return TE_OK;
+	if (L.xf_valid_for == fine) L.xf_valid_for = nullptr; // fine is overwritten
+	if (L.dim == 2) {
+		int rc = prepareGhosts2d(g, C, coarse);
+		if (rc) return rc;
+		Timed t(g, KC_PROLONG_QUADRATIC, (size_t) L.P * L.nc);
+		hipLaunchKernelGGL(k_prolong_quadratic2d, dim3(gridFor((size_t) L.P * L.nc / 2, 256, 65536)), dim3(256), 0, g->stream, C.dev2(), L.P,
+		                   L.parent.p, L.orth.p, coarse, fine);
+		HIPCHK(hipGetLastError());
+		return TE_OK;
+	}
+	switch (L.n) {
+		case 4: return prolongQuadraticN<4>(g, L, C, coarse, fine);
+		case 8: return prolongQuadraticN<8>(g, L, C, coarse, fine);
+		case 16: return prolongQuadraticN<16>(g, L, C, coarse, fine);
+		default: return prolongQuadraticN<32>(g, L, C, coarse, fine);
+	}
+}
 } // namespace tei
 
 extern "C" {
+int te_prolong_quadratic(te_gmg *g, int fine_level, const te_vec *coarse, te_vec *fine)
+{
+	return guarded([&]() -> int {
+		int rc;
+		if ((rc = checkLevelVec(g, fine_level, fine, "te_prolong_quadratic"))
+		    || (rc = checkLevelVec(g, fine_level + 1, coarse, "te_prolong_quadratic")))
+			return rc;
+		return doProlongQuadratic(g, fine_level, coarse->d, fine->d);
+	});
+}
+
 int te_prolong_linear_add(te_gmg *g, int fine_level, const te_vec *coarse, te_vec *fine)
 {
 	return guarded([&]() -> int {

@@ -599,6 +599,41 @@ int transferTables(const Hierarchy &H, const Level &lv, const Level &cv, const L
 	}
 	return TE_OK;
 }
+
+// LevelTables::brestrict. A child's physical side s is a physical side s of its parent, so the map follows from parent, orth and
+// the two levels' physical-face numbers.
+int boundaryRestrictTable(const Level &lv, const Level &cv, LevelTables &T)
+{
+	const int            D = lv.dim, NS = 2 * D, NQ = 1 << (D - 1);
+	std::vector<int32_t> cb;
+	const int            ncb = te::bfaceIndex(cv, cb);
+	T.brestrict.assign((size_t) ncb * 5, -1);
+	for (int p = 0; p < lv.P; p++) {
+		const int pc = T.parent[p], o = T.orth[p];
+		for (int s = 0; s < NS; s++) {
+			const int fb = T.bface[(size_t) p * NS + s];
+			if (fb < 0) continue;
+			const int c = cb[(size_t) pc * NS + s];
+			if (c < 0) return te::fail(TE_EINVAL, "te_gmg_create: a physical face whose parent has a neighbour there");
+			int32_t *row = &T.brestrict[(size_t) c * 5];
+			if (o < 0) {
+				row[0] = 1, row[1] = fb;
+				continue;
+			}
+			int q = 0, k = 0;
+			for (int a = 0; a < D; a++)
+				if (a != (s >> 1)) q |= ((o >> a) & 1) << k++;
+			row[0] = 0, row[1 + q] = fb;
+		}
+	}
+	for (int c = 0; c < ncb; c++) {
+		const int32_t *row = &T.brestrict[(size_t) c * 5];
+		bool           ok  = row[0] == 1 ? row[1] >= 0 : row[0] == 0;
+		for (int q = 0; ok && row[0] == 0 && q < NQ; q++) ok = row[1 + q] >= 0;
+		if (!ok) return te::fail(TE_EINVAL, "te_gmg_create: a coarse physical face that its children do not cover");
+	}
+	return TE_OK;
+}
 } // namespace
 
 int computeLevelTables(const Hierarchy &H, int li, const LevelBuildOpts &opt, LevelTables &T)
@@ -629,6 +664,8 @@ int computeLevelTables(const Hierarchy &H, int li, const LevelBuildOpts &opt, Le
 	T.fuse2_ok = (D == 3 && coarser && lv.P_global >= 256); // (TE_NO_FUSE2 is looked at where the path is chosen)
 	solvePlans(keys, T);
 	T.coarser = coarser;
-	return coarser ? transferTables(H, lv, H.levels[li + 1], opt, recvs, T) : TE_OK;
+	if (!coarser) return TE_OK;
+	if (int rc = transferTables(H, lv, H.levels[li + 1], opt, recvs, T)) return rc;
+	return H.nranks == 1 ? boundaryRestrictTable(lv, H.levels[li + 1], T) : TE_OK; // (every parent is local)
 }
 } // namespace tei

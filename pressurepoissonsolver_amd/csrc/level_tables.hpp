@@ -57,6 +57,10 @@ struct LevelTables {
 	// physical faces (mesh.hpp bfaceIndex), passed through
 	int                  nbf = 0;
 	std::vector<int32_t> bface;
+	// te_boundary_restrict (single rank, a coarser level exists): one row of 5 per physical face of the COARSER level, in its
+	// boundary-vector order: [0] 1 = a patch that copies through ([1] = its block on this level), 0 = the mean of the blocks
+	// [1 + q] of the children, q = the child's orthant bits on the face's remaining axes (the lower axis in bit 0)
+	std::vector<int32_t> brestrict;
 };
 
 /// fills `out` for level li of H as rank H.rank sees it; TE_OK, or an error code with te::fail's message

@@ -65,6 +65,15 @@ def bicgstab_host(gmg, x, b, opts=None, max_it=1000, tol=1e-12, allreduce=None):
     return its, rnorm / r0_norm
 
 
+def fmg(gmg, f, u, opts=None, bdata=None, cycles=2):
+    """Full multigrid (te_fmg): u to discretisation accuracy from the INTERIOR right-hand side f and the boundary vector bdata
+    (None: homogeneous data). opts None: V(1,1) with RB-GS; the solver's interpolator should be capi.INTERP_LINEAR for two cycles
+    per level to be enough. Single rank. Returns the relative residual."""
+    if opts is None:
+        opts = gmg.default_opts(smoother=capi.SMOOTH_RBGS)
+    return gmg.fmg(f, u, opts, bdata=bdata, cycles=cycles)
+
+
 def schur_solve(gmg, f, u, prec=None, max_it=1000, tol=1e-12, gamma=None, level=0):
     """The reference's --schur route (apps/3d/steady.cpp:336-420): BiCGStab on the interface system S gamma = g, right-
     preconditioned by PolyChebPrec when prec == "cheb", then u = Solve(f, gamma). Single rank. `gamma` (optional): an
