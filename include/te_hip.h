@@ -49,6 +49,32 @@ int te_mesh_dim(const te_mesh *m);
  * ilp[N][3] = id, level, parent; lengths/starts [N][dim]; nbr [N][2*dim]; child [N][2^dim] */
 int  te_mesh_get_nodes(const te_mesh *m, int32_t *ilp, double *lengths, double *starts,
                        int32_t *nbr, int32_t *child);
+/* The leaves (nodes without children): their number, and their ids in ascending order (ids[te_mesh_num_leaves]). Level 0 of every
+ * hierarchy built from the mesh holds exactly these nodes. */
+int te_mesh_num_leaves(const te_mesh *m);
+int te_mesh_leaves(const te_mesh *m, int32_t *ids);
+/* 1: the tree is FACE-balanced -- two leaves that share a face differ by at most one level (faces are all the solver reads; edges
+ * and corners are not looked at); 0: it is not; < 0: error. The reference never checks (its mesh files are balanced by whoever wrote
+ * them). */
+int te_mesh_is_balanced(const te_mesh *m);
+/* Adaptive regridding: *out = a NEW tree made from `m` (untouched) and one flag per named leaf, flags[i] for leaf ids[i]: +1 refine,
+ * 0 keep, -1 coarsen; leaves not named count as 0. TE_EINVAL for an unknown id, a node that is not a leaf, an id named twice or any
+ * other flag value. The reference has Tree::refineNode (OctTree.h:180) and nothing else: no balance, no coarsening. The rule:
+ *   1. Refinement set R. Start with the leaves flagged +1. Repeat until nothing changes: for every X in R and every side s such that
+ *      X has no same-level neighbour on s, s is an outer side of X's orthant in its parent, and X's parent has a neighbour Y on s that
+ *      is a leaf: add Y to R (a flag of -1 on Y loses). With a balanced `m` every leaf is refined at most once and *out is balanced;
+ *      with an unbalanced `m` *out may be unbalanced -- nothing is repaired.
+ *   2. Coarsening. A node P is coarsened when all 2^dim children of P are leaves, all of them are flagged -1, none of them is in R,
+ *      and for every side s of P the same-level neighbour Q = nbr[s] of P is absent, or a leaf that is not in R, or split with each of
+ *      Q's children on side s^1 a leaf that is not in R. Every family is judged against the state after step 1, not against the
+ *      other families: two adjacent families may both go.
+ *   3. Apply. R is refined in ascending (depth, id) order, each node as Tree::refineNode does it, so the new ids are ++max_id in that
+ *      order and then orthant order (max_id = the largest id of `m`). Then the accepted families are removed in ascending parent id:
+ *      the children are erased, P becomes a leaf, and the erased ids are cleared from their neighbours' nbr[]. num_levels is
+ *      recomputed. Surviving nodes keep their ids, so ids may have gaps afterwards (te_mesh_get_nodes lists rows in ascending id).
+ * Flagging every leaf +1 gives, node for node and id for id, what te_mesh_refine_leaves gives. A leaf changes by at most one level
+ * per call. */
+int te_mesh_adapt(const te_mesh *m, int count, const int32_t *ids, const int32_t *flags, te_mesh **out);
 void te_mesh_destroy(te_mesh *m);
 
 /* ----------------------------------------------------- level hierarchy (host only, no GPU) */
@@ -104,6 +130,11 @@ int te_hier_level_tables(const te_hier *h, int level, int32_t *id, int32_t *rank
                          int32_t *nbr_orth, int32_t *parent, int32_t *orth_on_parent);
 /* local -> global patch index of this rank's patches */
 int  te_hier_level_l2g(const te_hier *h, int level, int32_t *l2g);
+/* Where the patches of level 0 (= the leaves of the mesh) sit in the TREE, global order, P_global entries each: id = the tree node
+ * id, tree_parent = the id of its parent in the tree (-1: the root), orthant = its orthant there (-1: the root). Not the `parent`
+ * column of te_hier_level_tables, which names a patch of the next coarser LEVEL. Any pointer may be NULL. What te_vec_regrid matches
+ * two meshes by; replaces nothing in the reference (it never moves a solution between meshes). */
+int  te_hier_leaf_tree(const te_hier *h, int32_t *id, int32_t *tree_parent, int32_t *orthant);
 /* The interfaces of a level, the unknowns of the Schur-complement route: SchurHelper<D>::indexDomainIfacesLocal
  * (SchurHelper.h:377-397), the first-seen order of SchurInfo<D>::getIds() over the patches in this library's order.
  * iface_index[P][2*dim] = the interface patch p sees on side s, -1 on a physical face. Single-rank hierarchies only
@@ -302,6 +333,37 @@ int te_prolong_quadratic(te_gmg *g, int fine_level, const te_vec *coarse, te_vec
  * te_bicgstab, and the result is defined up to a constant. TE_EINVAL: vectors of the wrong kind, level or solver, cycles < 0;
  * TE_ESTATE: a sharded hierarchy (single rank only), or a coarsest level of more than one patch (max_levels / patches_per_proc). */
 int te_fmg(te_gmg *g, const te_cycle_opts *o, const te_vec *f, const te_vec *bdata, te_vec *u, int cycles, double *rel_resid);
+
+/* Regridding on the device: what a driver that adapts its mesh every few steps needs next to te_mesh_adapt. Neither call replaces
+ * anything in the reference, which has no error indicator and never carries a solution from one mesh to another.
+ *
+ * te_patch_indicator: out_host[p], p = this rank's patches of `level` in local order (P_local doubles, host memory), = the largest
+ * undivided second difference of u inside patch p: the maximum over the axes a, and over the cells c of the patch whose index along a
+ * lies in 1 .. n-2, of |(u[c - e_a] + u[c + e_a]) - 2 u[c]|. Patch-local: no ghosts, no exchange, so it runs on sharded hierarchies
+ * too (local patches). In that association the value does not depend on FMA contraction (2 u is exact) and a maximum does not depend
+ * on order: the result is reproducible bit for bit. One workgroup per patch (3D levels with few patches: per z-slab, then a
+ * fixed-order maximum); wave shuffles, LDS, one value per patch, no atomics. Synchronises the solver's stream. u is not modified.
+ * TE_EINVAL: not a domain vector of `level` of this solver, NULL. */
+int te_patch_indicator(te_gmg *g, int level, const te_vec *u, double *out_host);
+/* te_vec_regrid: u_dst = the transfer of u_src from src's mesh to dst's mesh. Both are level-0 domain vectors of their solvers; the
+ * solvers have the same dim and n, live on the same device and are single rank. Runs on dst's stream after a synchronisation of src's
+ * stream; u_src is not modified; neither solver's state changes (a te_vcycle afterwards gives the bits it gave before). The meshes
+ * must be one te_mesh_adapt apart (or the same): per destination leaf L (te_hier_leaf_tree), matched by node id and checked by
+ * position and size,
+ *   copy     L is a source leaf: the source patch, bit for bit.
+ *   refine   L's tree parent is a source leaf X, L its orthant o, e = X's values. The extended block E on indices -1 .. n per axis is
+ *            filled axis by axis, x then y then z: E[-1] = 3 e[0] - 3 e[1] + e[2], E[n] = 3 e[n-1] - 3 e[n-2] + e[n-3], later axes
+ *            extrapolating the ghosts of earlier axes as well (a tensor product; EVERY patch face is treated one-sided, neighbour or
+ *            not, so no ghost of the source hierarchy is read). Then, per axis a with c = (i + o_a n) >> 1 and d = -1 (i even) / +1 (i
+ *            odd): v <- (30 E[c] + 5 E[c + d] - 3 E[c - d]) / 32, x then y then z -- te_prolong_quadratic's weights and march.
+ *            Tensor-product quadratics are reproduced on every cell (order 3).
+ *   coarsen  the 2^dim source leaves whose tree parent is L: exactly the bits te_restrict (AvgRstr.h:78-113) writes for that parent
+ *            from those children.
+ * The map (one row per destination patch) is built on the host at every call and uploaded. One writer per destination cell, no
+ * atomics. TE_ESTATE (the message says "sharded") when either hierarchy is sharded; TE_EINVAL for NULL, a vector of the wrong kind,
+ * level or solver, different n / dim / device, or a destination leaf that has no source under the three cases above -- the message
+ * names its node id. */
+int te_vec_regrid(te_gmg *src, const te_vec *u_src, te_gmg *dst, te_vec *u_dst);
 
 /* The TE_* switches (docs/SWITCHES.md) are read from the environment once, in te_gmg_create. This call sets (value) or
  * clears (NULL) one of them for this solver afterwards -- how the tests pin one implementation against another. TE_ESTATE

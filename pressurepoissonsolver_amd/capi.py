@@ -63,6 +63,10 @@ SYMBOLS = {
     "te_mesh_num_levels": (_I, [_P]),
     "te_mesh_dim": (_I, [_P]),
     "te_mesh_get_nodes": (_I, [_P, _P, _P, _P, _P, _P]),
+    "te_mesh_num_leaves": (_I, [_P]),
+    "te_mesh_leaves": (_I, [_P, _P]),
+    "te_mesh_is_balanced": (_I, [_P]),
+    "te_mesh_adapt": (_I, [_P, _I, _P, _P, C.POINTER(_P)]),
     "te_mesh_destroy": (None, [_P]),
     "te_hier_build": (_I, [_P, _I, _I, _I, _D, _I, _I, C.POINTER(_P)]),
     "te_hier_build_placed": (_I, [_P, _I, _I, _I, _D, _I, _I, _D, _I, _I, C.POINTER(_P)]),
@@ -79,6 +83,7 @@ SYMBOLS = {
     "te_hier_level_replicated": (_I, [_P, _I]),
     "te_hier_level_tables": (_I, [_P, _I] + [_P] * 10),
     "te_hier_level_l2g": (_I, [_P, _I, _P]),
+    "te_hier_leaf_tree": (_I, [_P, _P, _P, _P]),
     "te_hier_num_ifaces": (_I, [_P, _I, C.POINTER(_I)]),
     "te_hier_iface_index": (_I, [_P, _I, _P]),
     "te_hier_destroy": (None, [_P]),
@@ -124,6 +129,8 @@ SYMBOLS = {
     "te_prolong_quadratic": (_I, [_P, _I, _P, _P]),
     "te_boundary_restrict": (_I, [_P, _I, _P, _P]),
     "te_fmg": (_I, [_P, _P, _P, _P, _P, _I, _PD]),
+    "te_patch_indicator": (_I, [_P, _I, _P, _P]),
+    "te_vec_regrid": (_I, [_P, _P, _P, _P]),
     "te_gmg_set_interpolator": (_I, [_P, _I]),
     "te_gmg_interpolator": (_I, [_P]),
     "te_vcycle": (_I, [_P, C.POINTER(CycleOpts), _P, _P]),
@@ -253,6 +260,30 @@ class Mesh:
                                       _ptr(out["nbr"]), _ptr(out["child"])))
         return out
 
+    def leaves(self):
+        """ids of the leaves, ascending (level 0 of every hierarchy built from this mesh holds exactly these)"""
+        n = lib().te_mesh_num_leaves(self.h)
+        if n < 0:
+            check(n)
+        out = np.zeros(n, np.int32)
+        check(lib().te_mesh_leaves(self.h, _ptr(out)))
+        return out
+
+    def is_balanced(self):
+        """face-balanced: two leaves that share a face differ by at most one level"""
+        r = lib().te_mesh_is_balanced(self.h)
+        if r < 0:
+            check(r)
+        return bool(r)
+
+    def adapt(self, flags):
+        """te_mesh_adapt: a NEW mesh from {leaf id: +1 refine / 0 keep / -1 coarsen} (leaves not named: 0); self is untouched"""
+        ids = np.array(list(flags.keys()), np.int32)
+        fl = np.array([flags[k] for k in flags], np.int32)
+        h = C.c_void_p()
+        check(lib().te_mesh_adapt(self.h, len(ids), _ptr(ids), _ptr(fl), C.byref(h)))
+        return Mesh(h)
+
     def __del__(self):
         if getattr(self, "h", None) and _lib is not None:
             _lib.te_mesh_destroy(self.h)
@@ -335,6 +366,13 @@ class Hierarchy:
             "orth_on_parent")]))
         return t
 
+    def leaf_tree(self):
+        """where the level-0 patches (= the mesh's leaves) sit in the tree, global order: dict(id, tree_parent, orthant)"""
+        P = self.sizes(0)[1]
+        t = dict(id=np.zeros(P, np.int32), tree_parent=np.zeros(P, np.int32), orthant=np.zeros(P, np.int32))
+        check(lib().te_hier_leaf_tree(self.h, _ptr(t["id"]), _ptr(t["tree_parent"]), _ptr(t["orthant"])))
+        return t
+
     def num_ifaces(self, level=0):
         """interfaces of the level (SchurHelper.h:377-397); single-rank hierarchies only"""
         out = C.c_int()
@@ -371,6 +409,12 @@ class Hierarchy:
         if getattr(self, "h", None) and _lib is not None:
             _lib.te_hier_destroy(self.h)
             self.h = None
+
+
+def regrid(src_g, u_src, dst_g, u_dst):
+    """te_vec_regrid: u_dst (level 0 of dst_g) = u_src (level 0 of src_g) carried to dst_g's mesh, one te_mesh_adapt away:
+    copy / quadratic refinement / AvgRstr coarsening per destination leaf"""
+    check(lib().te_vec_regrid(src_g.h, u_src.h, dst_g.h, u_dst.h))
 
 
 def face_vector_size(n, dim):
@@ -663,6 +707,12 @@ class GMG:
         rr = C.c_double()
         check(lib().te_fmg(self.h, C.byref(opts), f.h, bdata.h if bdata is not None else None, u.h, int(cycles), C.byref(rr)))
         return rr.value
+
+    def patch_indicator(self, u, level=0):
+        """te_patch_indicator: per local patch, the largest undivided second difference of u inside the patch"""
+        out = np.zeros(max(self.hier.sizes(level)[0], 1), np.float64)
+        check(lib().te_patch_indicator(self.h, level, u.h, _ptr(out)))
+        return out[:self.hier.sizes(level)[0]]
 
     def set_interpolator(self, kind):
         """which prolongation cycle() and bicgstab() use: INTERP_DIRECT (default) or INTERP_LINEAR"""

@@ -79,6 +79,33 @@ int te_mesh_get_nodes(const te_mesh *m, int32_t *ilp, double *lengths, double *s
 	}
 	return TE_OK;
 }
+int te_mesh_num_leaves(const te_mesh *m) { return m ? (int) m->tree.leaves().size() : TE_EINVAL; }
+int te_mesh_leaves(const te_mesh *m, int32_t *ids)
+{
+	if (!m || !ids) return te::fail(TE_EINVAL, "te_mesh_leaves: null argument");
+	size_t i = 0;
+	for (int id : m->tree.leaves()) ids[i++] = id;
+	return TE_OK;
+}
+int te_mesh_is_balanced(const te_mesh *m)
+{
+	if (!m) return te::fail(TE_EINVAL, "te_mesh_is_balanced: null mesh");
+	try {
+		return m->tree.isBalanced() ? 1 : 0;
+	} catch (const std::exception &e) { // (a link to a node that does not exist: a damaged file)
+		return te::fail(TE_EINVAL, std::string("te_mesh_is_balanced: ") + e.what());
+	}
+}
+int te_mesh_adapt(const te_mesh *m, int count, const int32_t *ids, const int32_t *flags, te_mesh **out)
+{
+	if (!m || !out) return te::fail(TE_EINVAL, "te_mesh_adapt: null argument");
+	try {
+		*out = new te_mesh{m->tree.adapt(count, ids, flags)};
+		return TE_OK;
+	} catch (const std::exception &e) {
+		return te::fail(TE_EINVAL, e.what());
+	}
+}
 void te_mesh_destroy(te_mesh *m) { delete m; }
 
 int te_hier_build_placed(const te_mesh *m, int n, int neumann, int max_levels, double patches_per_proc,
@@ -192,6 +219,14 @@ int te_hier_level_l2g(const te_hier *h, int level, int32_t *l2g)
 	if (!h || level < 0 || level >= (int) h->h.levels.size() || (!l2g && !h->h.levels[level].l2g.empty()))
 		return te::fail(TE_EINVAL, "te_hier_level_l2g: bad argument"); // (a rank without patches on the level may pass NULL)
 	copyOut(l2g, h->h.levels[level].l2g);
+	return TE_OK;
+}
+int te_hier_leaf_tree(const te_hier *h, int32_t *id, int32_t *tree_parent, int32_t *orthant)
+{
+	if (!h) return te::fail(TE_EINVAL, "te_hier_leaf_tree: null hierarchy");
+	copyOut(id, h->h.leaf_id);
+	copyOut(tree_parent, h->h.leaf_parent);
+	copyOut(orthant, h->h.leaf_orth);
 	return TE_OK;
 }
 int te_hier_num_ifaces(const te_hier *h, int level, int *out)

@@ -9,7 +9,8 @@ const char *kclassName[KC_COUNT] = {"stencil_apply", "stencil_resid", "stencil_j
                                     "stencil_rbgs_slabs", "stencil_slabs", "patch_solve_3pass", "rbgs_zero_resid_restrict",
                                     "restrict_fixup", "rbgs_resweep_prolong", "rbgs_zero_resid_restrict_faces",
                                     "rbgs_resweep_prolong_fcorr", "rbgs_zero_resid_restrict_faces_fcorr", "fcorr_gather", "patch_solve_mfma_faces",
-                                    "bicg_update", "bicg_s", "bicg_p", "stencil_apply_dot", "patch_bcgs", "gradient", "divergence", "project", "prolong_linear", "prolong_quadratic", "boundary_restrict"};
+                                    "bicg_update", "bicg_s", "bicg_p", "stencil_apply_dot", "patch_bcgs", "gradient", "divergence", "project", "prolong_linear", "prolong_quadratic", "boundary_restrict",
+                                    "indicator", "regrid"};
 const char *optName[O_COUNT] = {"TE_2D_SIMPLE", "TE_2D_NO_MFMA", "TE_2D_NO_PF", "TE_2D_NO_MR_FUSE", "TE_2D_TPB", "TE_NO_FUSE2", "TE_NO_FUSE3",
                                 "TE_NO_FUSE3_CF", "TE_NO_CFP", "TE_NO_XF", "TE_NO_FCORR", "TE_NO_FCORR_CF", "TE_NO_GTAB", "TE_NO_OVERLAP",
                                 "TE_OVERLAP_MIN", "TE_NO_PS_FACES", "TE_PS_MODE", "TE_PS_SLOW", "TE_RBGS_NOSLAB", "TE_ZS_FORCE", "TE_NO_ZS8",
@@ -167,6 +168,8 @@ int te_gmg_create(const te_hier *h, int device, te_gmg **out)
 		g->placement[0] = h->h.agglomerate, g->placement[1] = h->h.agglomerate_max, g->placement[2] = h->h.replicate;
 		g->placement[3] = (double) h->h.levels.size();
 		g->placement[4] = (double) h->h.neumann_sides;
+		g->leaf_id = h->h.leaf_id, g->leaf_parent = h->h.leaf_parent, g->leaf_orth = h->h.leaf_orth;
+		g->leaf_starts = h->h.levels[0].g_starts, g->leaf_lengths = h->h.levels[0].g_lengths;
 		memset(g->calls, 0, sizeof(g->calls));
 		memset(g->cells, 0, sizeof(g->cells));
 		memset(g->total_ms, 0, sizeof(g->total_ms));
@@ -246,6 +249,7 @@ void te_gmg_destroy(te_gmg *g)
 		if (v) te_vec_destroy(v);
 	fmgFree(g);
 	schurFree(g);
+	regridFree(g);
 	for (auto &e : g->ev_pool) {
 		(void) hipEventDestroy(e.a);
 		(void) hipEventDestroy(e.b);

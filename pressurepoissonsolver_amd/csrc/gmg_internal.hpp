@@ -12,6 +12,7 @@
 //   gmg_projection.hip face vectors, MAC gradient, divergence, pressure projection (projkernels.hpp)
 //   gmg_prolong.hip    the linear interpolator, the solver's choice of interpolator, the quadratic FMG interpolation (prolongkernels.hpp)
 //   gmg_fmg.hip        the full-multigrid solve te_fmg and its work vectors
+//   gmg_regrid.hip     the per-patch indicator te_patch_indicator and the transfer between two meshes te_vec_regrid (regridkernels.hpp)
 #pragma once
 #include "capi_common.hpp"
 #include "level_tables.hpp"
@@ -89,7 +90,10 @@ enum KClass : int {
 	KC_PROLONG_LINEAR,
 	// te_fmg's own kernels: the quadratic FMG interpolation (8 + 1 B per fine site plus halos; cells = fine sites) and the
 	// restriction of a boundary vector (cells = coarse boundary values)
-	KC_PROLONG_QUADRATIC, KC_BOUNDARY_RESTRICT, KC_COUNT
+	KC_PROLONG_QUADRATIC, KC_BOUNDARY_RESTRICT,
+	// regridding (regridkernels.hpp): the per-patch indicator (8 B per site) and the transfer between two meshes (16 B per copied
+	// site, about 9.4 per refined one, 72 per coarsened cell; cells = destination sites)
+	KC_INDICATOR, KC_REGRID, KC_COUNT
 };
 extern const char *kclassName[KC_COUNT]; // (gmg_core.hip)
 
@@ -416,6 +420,11 @@ struct te_gmg {
 	te_vec *bicg_work[8] = {nullptr}; // te_bicgstab's work vectors (level 0), allocated at its first call
 	struct FmgWs   *fmg   = nullptr;  // te_fmg's work vectors (gmg_fmg.hip), made at its first call
 	struct SchurWs *schur = nullptr;  // the Schur route's device tables and work vectors (gmg_schur.hip), made at its first use
+	struct RegridWs *regrid = nullptr; // the indicator's device output and the transfer's map (gmg_regrid.hip), made at their first use
+	// level 0 = the leaves of the mesh: tree node id, tree parent, orthant there, lower corner and lengths per patch (host copies of
+	// the hierarchy's te_hier_leaf_tree / level tables, global order): what te_vec_regrid matches two meshes by
+	std::vector<int32_t> leaf_id, leaf_parent, leaf_orth;
+	std::vector<double>  leaf_starts, leaf_lengths;
 	const PendingRhs *pending_rhs = nullptr; // set by te_bicgstab around a cycle: level 0's right-hand side is still to be formed
 	bool recording = false;
 	double bcgs_tol = 1e-12; // BiCGStabSolver(op, tol = 1e-12, max_it = 1000), BiCGStabSolver.h:103-108
@@ -710,6 +719,8 @@ int doProlongQuadratic(te_gmg *g, int fine_level, const double *coarse, double *
 int doBoundaryRestrict(te_gmg *g, int fine_level, const double *fine_bdata, double *coarse_bdata);
 // ---- gmg_fmg.hip
 void fmgFree(te_gmg *g); // (te_gmg_release_workspace, te_gmg_destroy)
+// ---- gmg_regrid.hip
+void regridFree(te_gmg *g); // (te_gmg_destroy)
 // ---- gmg_launch2d.hip
 int prepareGhosts2d(te_gmg *g, LevelHost &L, const double *u);
 template <int MODE> int launchStencil2d(te_gmg *g, LevelHost &L, const double *u, const double *f, double *out, double omega, int redmode = RED_NONE,

@@ -146,6 +146,121 @@ void Tree::refineLeaves()
 	num_levels++;
 }
 
+std::vector<int> Tree::leaves() const
+{
+	std::vector<int> out;
+	for (auto &p : nodes)
+		if (!p.second.hasChildren()) out.push_back(p.first);
+	return out;
+}
+
+// The tree stores same-level links only, so a pair of leaves two or more levels apart across a face shows from the coarse side: its
+// same-level neighbour is split, and that neighbour's child on the shared face is split again.
+bool Tree::isBalanced() const
+{
+	const int nsides = 2 * dim, north = 1 << dim;
+	for (auto &p : nodes) {
+		const Node &nd = p.second;
+		if (nd.hasChildren()) continue;
+		for (int s = 0; s < nsides; s++) {
+			if (nd.nbr[s] == -1) continue;
+			const Node &nb = nodes.at(nd.nbr[s]);
+			if (!nb.hasChildren()) continue;
+			for (int o = 0; o < north; o++)
+				if (orthOnSide(o, s ^ 1) && nodes.at(nb.child[o]).hasChildren()) return false;
+		}
+	}
+	return true;
+}
+
+Tree Tree::adapt(int count, const int32_t *ids, const int32_t *flags) const
+{
+	const int nsides = 2 * dim, north = 1 << dim;
+	if (count < 0 || (count > 0 && (!ids || !flags))) throw std::runtime_error("te_mesh_adapt: null ids or flags");
+	std::map<int, int> flag;
+	for (int i = 0; i < count; i++) {
+		auto it = nodes.find(ids[i]);
+		if (it == nodes.end()) throw std::runtime_error("te_mesh_adapt: unknown node id " + std::to_string(ids[i]));
+		if (it->second.hasChildren()) throw std::runtime_error("te_mesh_adapt: node " + std::to_string(ids[i]) + " is not a leaf");
+		if (flags[i] < -1 || flags[i] > 1)
+			throw std::runtime_error("te_mesh_adapt: flag " + std::to_string(flags[i]) + " on node " + std::to_string(ids[i]) + " (must be -1, 0 or +1)");
+		if (!flag.emplace(ids[i], flags[i]).second) throw std::runtime_error("te_mesh_adapt: node " + std::to_string(ids[i]) + " is named twice");
+	}
+	auto orthOf = [&](const Node &nd) {
+		const Node &par = nodes.at(nd.parent);
+		int         o   = 0;
+		while (par.child[o] != nd.id) o++;
+		return o;
+	};
+	// 1. the refinement set: the flagged leaves, and every coarser leaf across an outer face of one of them (repeated)
+	std::set<int>    R;
+	std::vector<int> todo;
+	for (auto &f : flag)
+		if (f.second == 1 && R.insert(f.first).second) todo.push_back(f.first);
+	while (!todo.empty()) {
+		const Node &x = nodes.at(todo.back());
+		todo.pop_back();
+		if (x.parent == -1) continue;
+		const Node &par = nodes.at(x.parent);
+		const int   o   = orthOf(x);
+		for (int s = 0; s < nsides; s++) {
+			if (x.nbr[s] != -1 || !orthOnSide(o, s) || par.nbr[s] == -1) continue;
+			const Node &y = nodes.at(par.nbr[s]);
+			if (!y.hasChildren() && R.insert(y.id).second) todo.push_back(y.id);
+		}
+	}
+	// 2. the families that go, every one judged against the state after step 1
+	auto goes = [&](int id) { // a leaf flagged -1 that step 1 did not claim
+		auto it = flag.find(id);
+		return it != flag.end() && it->second == -1 && !R.count(id);
+	};
+	auto quietLeaf = [&](int id) { return !nodes.at(id).hasChildren() && !R.count(id); };
+	std::vector<int> families;
+	for (auto &p : nodes) {
+		const Node &P = p.second;
+		if (!P.hasChildren()) continue;
+		bool ok = true;
+		for (int o = 0; o < north && ok; o++) ok = !nodes.at(P.child[o]).hasChildren() && goes(P.child[o]);
+		for (int s = 0; s < nsides && ok; s++) {
+			if (P.nbr[s] == -1) continue;
+			const Node &Q = nodes.at(P.nbr[s]);
+			if (!Q.hasChildren()) {
+				ok = !R.count(Q.id);
+				continue;
+			}
+			for (int o = 0; o < north && ok; o++)
+				if (orthOnSide(o, s ^ 1)) ok = quietLeaf(Q.child[o]);
+		}
+		if (ok) families.push_back(P.id); // (ascending parent id: the map's order)
+	}
+	// 3. apply
+	Tree t = *this;
+	std::vector<std::pair<int, int>> order;
+	for (int id : R) order.emplace_back(depthOf(id), id);
+	std::sort(order.begin(), order.end());
+	for (auto &r : order) t.refineNode(r.second);
+	for (int pid : families) {
+		Node &P = t.nodes.at(pid);
+		for (int o = 0; o < north; o++) {
+			const Node c = t.nodes.at(P.child[o]);
+			for (int s = 0; s < nsides; s++) {
+				if (c.nbr[s] == -1) continue;
+				auto nb = t.nodes.find(c.nbr[s]); // (a sibling may be gone already)
+				if (nb != t.nodes.end() && nb->second.nbr[s ^ 1] == c.id) nb->second.nbr[s ^ 1] = -1;
+			}
+			t.nodes.erase(c.id);
+			P.child[o] = -1;
+		}
+	}
+	t.num_levels = 0;
+	t.max_id     = 0;
+	for (auto &p : t.nodes) {
+		t.num_levels = std::max(t.num_levels, p.second.level);
+		t.max_id     = std::max(t.max_id, p.first);
+	}
+	return t;
+}
+
 uint64_t mortonKey(const double *starts, const double *root_starts, const double *root_lengths,
                    int dim, int bits)
 {
@@ -380,6 +495,21 @@ Hierarchy Hierarchy::build(const Tree &t, int n, bool neumann, int max_levels,
 	}
 	if (nranks == 1)
 		for (auto &lv : h.levels) buildIfaces(lv);
+	{ // level 0 = the leaves: where each sits in the TREE (te_hier_leaf_tree, te_vec_regrid)
+		const Level &f = h.levels[0];
+		h.leaf_id = f.g_id;
+		h.leaf_parent.assign(f.P_global, -1);
+		h.leaf_orth.assign(f.P_global, -1);
+		for (int p = 0; p < f.P_global; p++) {
+			const Node &nd = t.nodes.at(f.g_id[p]);
+			if (nd.parent == -1) continue;
+			const Node &par = t.nodes.at(nd.parent);
+			int         o   = 0;
+			while (par.child[o] != nd.id) o++;
+			h.leaf_parent[p] = nd.parent;
+			h.leaf_orth[p]   = o;
+		}
+	}
 	return h;
 }
 

@@ -56,6 +56,14 @@ struct Tree {
 	void refineLeaves();
 	void refineNode(int id);
 	int  depthOf(int id) const;
+	/// ids of the leaves, ascending
+	std::vector<int> leaves() const;
+	/// face-balanced: two leaves that share a face differ by at most one level (faces are all the solver reads)
+	bool isBalanced() const;
+	/// A new tree from per-leaf flags (+1 refine, 0 keep, -1 coarsen; leaves not named: 0); *this is untouched. The rule is stated
+	/// in include/te_hip.h (te_mesh_adapt). Throws std::runtime_error for an unknown id, a non-leaf, a duplicate or another flag value.
+	/// The reference has refineNode (OctTree.h:180) only: no balance, no coarsening.
+	Tree adapt(int count, const int32_t *ids, const int32_t *flags) const;
 };
 
 enum NbrKind : int32_t { NBR_NONE = 0, NBR_NORMAL = 1, NBR_COARSE = 2, NBR_FINE = 3 };
@@ -129,6 +137,9 @@ struct Hierarchy {
 	/// must agree on (te_gmg checks it across the ranks before the first cycle)
 	double agglomerate = 64.0;
 	int    agglomerate_max = 64, replicate = 1;
+	/// Level 0 holds exactly the tree's leaves. Per level-0 patch (global order): its tree node id, the id of its parent IN THE TREE
+	/// (-1: the root) and its orthant there (-1: the root) -- what a transfer between two meshes needs (te_vec_regrid). Host only.
+	std::vector<int32_t> leaf_id, leaf_parent, leaf_orth;
 
 	/// Build every level the reference's CycleFactory would build
 	/// (CycleFactory3d.cpp:69-134): finest first, then coarser tree levels while
