@@ -11,12 +11,7 @@ template <int N>
 int zeroSweepResidN(te_gmg *g, LevelHost &L, const double *f, double *out, double *coarse, double *xf_out, bool store_u,
                     double *fcorr_out, const double *fcorr_in, const PendingRhs *fs)
 {
-	RestrictDst rd = RestrictDst();
-	rd.parent     = L.parent.p;
-	rd.orth       = L.orth.p;
-	rd.coarse     = coarse;
-	rd.remote     = L.upbuf.p;
-	rd.remote_off = L.up_off.p;
+	RestrictDst rd = restrictDst(L, coarse);
 	// the patches export the 2x2 sums of their face layers (rs6); what lies behind a ghost slot, and a copy-through patch's own faces,
 	// the gather kernel forms from the slot / the face layers
 	// (round 6: on refined levels too -- the kernel's export does not look at what a patch is, a same-level neighbour's finished sums
@@ -35,7 +30,7 @@ int zeroSweepResidN(te_gmg *g, LevelHost &L, const double *f, double *out, doubl
 		Timed      t(g, store_u ? KC_ZERO_RESID : (fcorr_in ? KC_ZERO_RESID_FACES_FCORR : KC_ZERO_RESID_FACES), (size_t) L.P * L.nc, true);
 		if (!store_u) L.f6_tab = L.f6off.p != nullptr && !g->cfg.has(O_PACK_FACES); // the face layers go where the level's table puts them
 		LevelDev   D = L.dev();
-		const dim3 grid(8 * ((L.P + 7) / 8)), blk(Tile3<N>::TPB);
+		const dim3 grid = slabGrid(L.P), blk(Tile3<N>::TPB);
 		if (store_u) {
 			D.xf_out = xf_out;
 			launchT(t, (k_rbgs_zero_resid3d<N, true>), grid, blk, 0, g->stream, D, f, out, rd, FSrc());
@@ -126,17 +121,14 @@ int zeroSweepResidN(te_gmg *g, LevelHost &L, const double *f, double *out, doubl
 template <int N>
 int resweepProlongN(te_gmg *g, LevelHost &L, const double *f, double *out, const double *prolong_from, double *xf_out, const double *fcorr_in)
 {
-	ProlongSrc ps;
-	ps.parent = L.parent.p;
-	ps.orth   = L.orth.p;
-	ps.coarse = prolong_from;
-	auto launch = [&](LevelDev D) {
+	ProlongSrc ps     = prolongSrc(L, prolong_from);
+	auto       launch = [&](LevelDev D) {
 		if (D.count == 0) return;
 		Timed t(g, fcorr_in ? KC_RESWEEP_FCORR : KC_RESWEEP, (size_t) D.count * L.nc, true);
 		D.f6    = L.f6buf.p;
 		D.fcorr = fcorr_in;
 		if constexpr (N >= 4) {
-			const dim3  grid(8 * ((D.count + 7) / 8)), blk(Tile3<N>::TPB);
+			const dim3  grid = slabGrid(D.count), blk(Tile3<N>::TPB);
 			// tuning variants (march3d.hpp), all bit-identical. Defaults, each measured: the finest level stores u non-temporally
 			// (nobody re-reads it) and loads f non-temporally unless f can still be in the Infinity Cache from the pre-sweep
 			// that read it (19 instead of 27: 256^3, a rank's share at eight ranks; 53.4 -> 49.0 us at 256^3); a large finest
@@ -213,12 +205,7 @@ int resweepProlong(te_gmg *g, LevelHost &L, const double *f, double *out, const 
                    const double *fcorr_in)
 {
 	if (L.dim == 2) return resweepProlong2d(g, L, f, out, prolong_from);
-	switch (L.n) {
-		case 4: return resweepProlongN<4>(g, L, f, out, prolong_from, xf_out, fcorr_in);
-		case 8: return resweepProlongN<8>(g, L, f, out, prolong_from, xf_out, fcorr_in);
-		case 16: return resweepProlongN<16>(g, L, f, out, prolong_from, xf_out, fcorr_in);
-		default: return resweepProlongN<32>(g, L, f, out, prolong_from, xf_out, fcorr_in);
-	}
+	return dispatchN(L.n, [&](auto n) { return resweepProlongN<decltype(n)::value>(g, L, f, out, prolong_from, xf_out, fcorr_in); });
 }
 
 // opts.fuse = 2 with the block-Jacobi smoother: after an exact patch solve from the zero iterate the residual
@@ -229,12 +216,7 @@ int resweepProlong(te_gmg *g, LevelHost &L, const double *f, double *out, const 
 // compact x faces or null; coarse: the coarse level's f with `coarse_n` entries.
 template <int N> int interfaceResidRestrictN(te_gmg *g, LevelHost &L, const double *u, const double *xf, double *coarse, size_t coarse_n)
 {
-	RestrictDst rd = RestrictDst();
-	rd.parent     = L.parent.p;
-	rd.orth       = L.orth.p;
-	rd.coarse     = coarse;
-	rd.remote     = L.upbuf.p;
-	rd.remote_off = L.up_off.p;
+	RestrictDst rd = restrictDst(L, coarse);
 	int rc;
 	L.pack_f6 = L.ps_faces ? L.f6buf.p : nullptr; // (the iterate exists only as its face layers)
 	rc        = prepareGhosts<N>(g, L, u);
@@ -265,12 +247,7 @@ template <int N> int interfaceResidRestrictN(te_gmg *g, LevelHost &L, const doub
 
 int interfaceResidRestrict(te_gmg *g, LevelHost &L, const double *u, const double *xf, double *coarse, size_t coarse_n)
 {
-	switch (L.n) {
-		case 4: return interfaceResidRestrictN<4>(g, L, u, xf, coarse, coarse_n);
-		case 8: return interfaceResidRestrictN<8>(g, L, u, xf, coarse, coarse_n);
-		case 16: return interfaceResidRestrictN<16>(g, L, u, xf, coarse, coarse_n);
-		default: return interfaceResidRestrictN<32>(g, L, u, xf, coarse, coarse_n);
-	}
+	return dispatchN(L.n, [&](auto n) { return interfaceResidRestrictN<decltype(n)::value>(g, L, u, xf, coarse, coarse_n); });
 }
 
 int zeroSweepResid(te_gmg *g, LevelHost &L, const double *f, double *out, double *coarse, double *xf_out, bool store_u,
@@ -278,11 +255,8 @@ int zeroSweepResid(te_gmg *g, LevelHost &L, const double *f, double *out, double
 {
 	if (L.dim == 2) return zeroSweepResid2d(g, L, f, out, coarse, store_u, fold_in, skip_fixup);
 	if ((fold_in && fold_in->fine) || skip_fixup) return te::fail(TE_ESTATE, "zeroSweepResid: the folded fix-up exists in 2D only");
-	switch (L.n) {
-		case 4: return zeroSweepResidN<4>(g, L, f, out, coarse, xf_out, store_u, fcorr_out, fcorr_in, fs);
-		case 8: return zeroSweepResidN<8>(g, L, f, out, coarse, xf_out, store_u, fcorr_out, fcorr_in, fs);
-		case 16: return zeroSweepResidN<16>(g, L, f, out, coarse, xf_out, store_u, fcorr_out, fcorr_in, fs);
-		default: return zeroSweepResidN<32>(g, L, f, out, coarse, xf_out, store_u, fcorr_out, fcorr_in, fs);
-	}
+	return dispatchN(L.n, [&](auto n) {
+		return zeroSweepResidN<decltype(n)::value>(g, L, f, out, coarse, xf_out, store_u, fcorr_out, fcorr_in, fs);
+	});
 }
 } // namespace tei

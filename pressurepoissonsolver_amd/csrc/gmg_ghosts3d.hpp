@@ -1,7 +1,9 @@
 // Shared by the 3D launch units (gmg_launch3d.hip, gmg_fused3d.hip, gmg_patchsolve.hip): making a level's ghost planes current
 // around a kernel launch -- pack, face exchange (or the interior / boundary split around it), coarse/fine ghosts -- and shipping
-// restricted blocks to the ranks that hold the parents. Templates on the patch size, instantiated where they are used.
+// restricted blocks to the ranks that hold the parents. Templates on the patch size, instantiated where they are used. Also what
+// every 3D launch site shares: the slab rules, the grid, the builders of the kernels' argument structs (dispatch.hpp: the dispatch).
 #pragma once
+#include "dispatch.hpp"
 #include "gmg_internal.hpp"
 
 namespace tei
@@ -129,15 +131,52 @@ template <int N, class F> int withGhosts(te_gmg *g, LevelHost &L, const double *
 	return TE_OK;
 }
 
-// z-slabs per patch on levels with few patches: the rule of launchStencilN (the MAC operators, the linear prolongation)
-template <int N> inline int projSlabs(const te_gmg *g, int P)
+// z-slabs per patch for the stencil kernels (and the MAC operators, the interpolators, the regrid transfer): enough workgroups to
+// fill 256 CUs a few times over when the level has few patches
+template <int N> inline int stencilSlabs(const te_gmg *g, int P)
 {
 	int zs = 1;
 	if (N >= 8) {
 		while (zs < 4 && (g->cfg.has(O_ZS_FORCE) || (size_t) P * zs < 2048) && N / (zs * 2) >= 4) zs *= 2;
-		if (zs == 4 && N == 32 && P <= 64 && !g->cfg.has(O_NO_ZS8)) zs = 8;
+		if (zs == 4 && N == 32 && P <= 64 && !g->cfg.has(O_NO_ZS8)) zs = 8; // (see rbgsSlabs)
 	}
 	return zs;
+}
+
+// z-slabs per patch for the RB-GS kernels: enough workgroups to occupy 256 CUs x 4 when the level has few patches
+template <int N> inline int rbgsSlabs(const te_gmg *g, int count)
+{
+	int zs = 1;
+	while (zs < 4 && !g->cfg.has(O_RBGS_NOSLAB) && (size_t) count * zs < 1024 && N / (zs * 2) >= 4) zs *= 2;
+	// very few patches (the coarsest levels of a cycle): a kernel is one patch's march, a dependent chain of plane steps of
+	// ~1-2 us each that nothing hides -- eight slabs of four planes (six steps) instead of four of eight (ten steps)
+	if (zs == 4 && N == 32 && count <= 64 && !g->cfg.has(O_NO_ZS8)) zs = 8;
+	return zs;
+}
+
+// the grid of a launch over `count` patches in `zs` slabs each with Tile3<N>::TPB threads: whole multiples of eight workgroups
+inline dim3 slabGrid(int count, int zs = 1) { return dim3(8 * ((count * zs + 7) / 8)); }
+
+// where the restricting kernels put a patch's coarse block (kernels3d.hpp RestrictDst; rs6 stays the caller's business)
+inline RestrictDst restrictDst(const LevelHost &L, double *coarse)
+{
+	RestrictDst rd = RestrictDst();
+	rd.parent     = L.parent.p;
+	rd.orth       = L.orth.p;
+	rd.coarse     = coarse;
+	rd.remote     = L.upbuf.p;
+	rd.remote_off = L.up_off.p;
+	return rd;
+}
+
+// the iterate is u + P(coarse) (march3d.hpp ProlongSrc; cbase and gparent / gorth are set by the callers whose kernels read them)
+inline ProlongSrc prolongSrc(const LevelHost &L, const double *coarse)
+{
+	ProlongSrc ps;
+	ps.parent = L.parent.p;
+	ps.orth   = L.orth.p;
+	ps.coarse = coarse;
+	return ps;
 }
 
 // The restricted blocks of this rank's patches to the other ranks (the kernels before this have written them into the local

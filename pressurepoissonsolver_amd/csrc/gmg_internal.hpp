@@ -5,6 +5,7 @@
 //   gmg_core.hip       places them on the device (buildLevel), solver / vector life cycle, options, profiling, Init kernels
 //   gmg_transport.hip  exchanges between ranks: RCCL binding, host callback, direct-store transport, scalar reductions, watchdog
 //   gmg_launch3d.hip   every 3D kernel launch (stencil, sweeps, fused sweeps, patch solves, transfers)
+//   dispatch.hpp       patch size / z-slab count -> template instantiation of a 3D launch (dispatchN, dispatchSlabs): host C++ only
 //   gmg_launch2d.hip   the 2D twins
 //   gmg_cycle.hip      the cycle driver (GMG/Cycle.h, VCycle.h, WCycle.h), schedule check, te_gmg_autotune, per-operation entries
 //   gmg_krylov.hip     Vector<D> BLAS-1 entries and te_bicgstab (BiCGStab.h:45-106)

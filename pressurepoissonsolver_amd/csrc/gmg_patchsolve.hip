@@ -46,11 +46,8 @@ template <int N> int patchSolveN(te_gmg *g, LevelHost &L, const double *f, doubl
 		const double *xf_in = (g->in_cycle && !zero_guess) ? xfFor(L, u) : nullptr;
 		L.xf_valid_for      = nullptr; // u is rewritten in place
 		if (!zero_guess) {
-			ProlongSrc ps;
-			ps.parent = L.parent.p;
-			ps.orth   = L.orth.p;
-			ps.coarse = prolong_from;
-			L.pack_f6 = L.ps_faces ? L.f6buf.p : nullptr;
+			const ProlongSrc ps = prolongSrc(L, prolong_from);
+			L.pack_f6           = L.ps_faces ? L.f6buf.p : nullptr;
 			rc        = prepareGhosts<N>(g, L, u, prolong_from ? &ps : nullptr);
 			L.pack_f6 = nullptr;
 			if (rc) return rc;
@@ -131,7 +128,7 @@ template <int N> int patchSolveN(te_gmg *g, LevelHost &L, const double *f, doubl
 				if (xo) xfProduced(L, u);
 			}
 			if (n_mix > 0) {
-				const dim3 gf(8 * ((n_mix + 7) / 8));
+				const dim3 gf = slabGrid(n_mix);
 				if (zero_guess)
 					launchT(t, k_ps_fused<false>, gf, b512, PSF_LDS_BYTES, g->stream, n_mix, L.plan.p, L.mats.p, L.lam.p,
 					                   L.zero_mode.p, L.rh2.p, f, cp, u, lst_mix);
@@ -227,11 +224,6 @@ int patchSolve(te_gmg *g, LevelHost &L, const double *f, double *u, bool zero_gu
 		if (rc == TE_OK && *swapped && swapped == &dummy) return te::fail(TE_ESTATE, "patchSolve: 2D result left in scratch");
 		return rc;
 	}
-	switch (L.n) {
-		case 4: return patchSolveN<4>(g, L, f, u, s0, s1, zero_guess, prolong_from);
-		case 8: return patchSolveN<8>(g, L, f, u, s0, s1, zero_guess, prolong_from);
-		case 16: return patchSolveN<16>(g, L, f, u, s0, s1, zero_guess, prolong_from);
-		default: return patchSolveN<32>(g, L, f, u, s0, s1, zero_guess, prolong_from);
-	}
+	return dispatchN(L.n, [&](auto n) { return patchSolveN<decltype(n)::value>(g, L, f, u, s0, s1, zero_guess, prolong_from); });
 }
 } // namespace tei

@@ -30,23 +30,14 @@ static int faceGeom(LevelHost &L, const te_vec *bdata, FaceGeom *F)
 
 template <int N, bool PROJECT> static int gradientN(te_gmg *g, LevelHost &L, const FaceGeom &F, const double *u, double *G, double alpha)
 {
-	const int zs     = projSlabs<N>(g, L.P);
+	const int zs     = stencilSlabs<N>(g, L.P);
 	auto      launch = [&](LevelDev D) {
-        if (D.count == 0) return;
-        Timed      t(g, PROJECT ? KC_PROJECT : KC_GRADIENT, (size_t) D.count * L.nc);
-        const dim3 grid(8 * ((D.count * zs + 7) / 8)), blk(Tile3<N>::TPB);
-        switch (zs) {
-            case 1: hipLaunchKernelGGL((k_gradient3d<N, PROJECT, 1>), grid, blk, 0, g->stream, D, F, u, G, alpha); break;
-            case 2:
-                if constexpr (N >= 8) hipLaunchKernelGGL((k_gradient3d<N, PROJECT, 2>), grid, blk, 0, g->stream, D, F, u, G, alpha);
-                break;
-            case 8:
-                if constexpr (N >= 32) hipLaunchKernelGGL((k_gradient3d<N, PROJECT, 8>), grid, blk, 0, g->stream, D, F, u, G, alpha);
-                break;
-            default:
-                if constexpr (N >= 16) hipLaunchKernelGGL((k_gradient3d<N, PROJECT, 4>), grid, blk, 0, g->stream, D, F, u, G, alpha);
-                break;
-        }
+		if (D.count == 0) return;
+		Timed t(g, PROJECT ? KC_PROJECT : KC_GRADIENT, (size_t) D.count * L.nc);
+		dispatchSlabs<N>(zs, [&](auto z) {
+			hipLaunchKernelGGL((k_gradient3d<N, PROJECT, decltype(z)::value>), slabGrid(D.count, zs), dim3(Tile3<N>::TPB), 0, g->stream, D, F, u, G,
+			                   alpha);
+		});
 	};
 	int rc = withGhosts<N>(g, L, u, launch);
 	if (rc) return rc;
@@ -68,30 +59,16 @@ template <bool PROJECT> static int gradient(te_gmg *g, LevelHost &L, const te_ve
 		HIPCHK(hipGetLastError());
 		return TE_OK;
 	}
-	switch (L.n) {
-		case 4: return gradientN<4, PROJECT>(g, L, F, u->d, G->d, alpha);
-		case 8: return gradientN<8, PROJECT>(g, L, F, u->d, G->d, alpha);
-		case 16: return gradientN<16, PROJECT>(g, L, F, u->d, G->d, alpha);
-		default: return gradientN<32, PROJECT>(g, L, F, u->d, G->d, alpha);
-	}
+	return dispatchN(L.n, [&](auto n) { return gradientN<decltype(n)::value, PROJECT>(g, L, F, u->d, G->d, alpha); });
 }
 
 template <int N> static void divergenceN(te_gmg *g, LevelHost &L, const double *U, double *out, double alpha)
 {
-	const int  zs = projSlabs<N>(g, L.P);
-	const dim3 grid(8 * ((L.P * zs + 7) / 8)), blk(Tile3<N>::TPB);
-	switch (zs) {
-		case 1: hipLaunchKernelGGL((k_divergence3d<N, 1>), grid, blk, 0, g->stream, L.P, L.geom_h.p, U, out, alpha); break;
-		case 2:
-			if constexpr (N >= 8) hipLaunchKernelGGL((k_divergence3d<N, 2>), grid, blk, 0, g->stream, L.P, L.geom_h.p, U, out, alpha);
-			break;
-		case 8:
-			if constexpr (N >= 32) hipLaunchKernelGGL((k_divergence3d<N, 8>), grid, blk, 0, g->stream, L.P, L.geom_h.p, U, out, alpha);
-			break;
-		default:
-			if constexpr (N >= 16) hipLaunchKernelGGL((k_divergence3d<N, 4>), grid, blk, 0, g->stream, L.P, L.geom_h.p, U, out, alpha);
-			break;
-	}
+	const int zs = stencilSlabs<N>(g, L.P);
+	dispatchSlabs<N>(zs, [&](auto z) {
+		hipLaunchKernelGGL((k_divergence3d<N, decltype(z)::value>), slabGrid(L.P, zs), dim3(Tile3<N>::TPB), 0, g->stream, L.P, L.geom_h.p, U, out,
+		                   alpha);
+	});
 }
 } // namespace tei
 
@@ -153,12 +130,7 @@ int te_divergence(te_gmg *g, int level, double alpha, const te_vec *U, te_vec *o
 			hipLaunchKernelGGL(k_divergence2d, dim3(gridFor((size_t) L.P * L.nc / 2, 256, 65536)), dim3(256), 0, g->stream, L.P, L.n, L.geom_h.p,
 			                   (const double *) U->d, out->d, alpha);
 		} else {
-			switch (L.n) {
-				case 4: divergenceN<4>(g, L, U->d, out->d, alpha); break;
-				case 8: divergenceN<8>(g, L, U->d, out->d, alpha); break;
-				case 16: divergenceN<16>(g, L, U->d, out->d, alpha); break;
-				default: divergenceN<32>(g, L, U->d, out->d, alpha); break;
-			}
+			dispatchN(L.n, [&](auto n) { divergenceN<decltype(n)::value>(g, L, U->d, out->d, alpha); });
 		}
 		HIPCHK(hipGetLastError());
 		return TE_OK;

@@ -13,22 +13,13 @@ static const char *const kShardedWhy =
 
 template <int N> static int prolongLinearN(te_gmg *g, LevelHost &L, LevelHost &C, const double *coarse, double *fine)
 {
-	const int zs     = projSlabs<N>(g, L.P);
+	const int zs     = stencilSlabs<N>(g, L.P);
 	auto      launch = [&](LevelDev D) {
-        Timed      t(g, KC_PROLONG_LINEAR, (size_t) L.P * L.nc);
-        const dim3 grid(8 * ((L.P * zs + 7) / 8)), blk(Tile3<N>::TPB);
-        switch (zs) {
-            case 1: hipLaunchKernelGGL((k_prolong_linear3d<N, 1>), grid, blk, 0, g->stream, L.P, D, L.parent.p, L.orth.p, coarse, fine); break;
-            case 2:
-                if constexpr (N >= 8) hipLaunchKernelGGL((k_prolong_linear3d<N, 2>), grid, blk, 0, g->stream, L.P, D, L.parent.p, L.orth.p, coarse, fine);
-                break;
-            case 8:
-                if constexpr (N >= 32) hipLaunchKernelGGL((k_prolong_linear3d<N, 8>), grid, blk, 0, g->stream, L.P, D, L.parent.p, L.orth.p, coarse, fine);
-                break;
-            default:
-                if constexpr (N >= 16) hipLaunchKernelGGL((k_prolong_linear3d<N, 4>), grid, blk, 0, g->stream, L.P, D, L.parent.p, L.orth.p, coarse, fine);
-                break;
-        }
+		Timed t(g, KC_PROLONG_LINEAR, (size_t) L.P * L.nc);
+		dispatchSlabs<N>(zs, [&](auto z) {
+			hipLaunchKernelGGL((k_prolong_linear3d<N, decltype(z)::value>), slabGrid(L.P, zs), dim3(Tile3<N>::TPB), 0, g->stream, L.P, D, L.parent.p,
+			                   L.orth.p, coarse, fine);
+		});
 	};
 	// (one rank: the coarse level has no remote face, so withGhosts launches once, over the whole level's tables)
 	int rc = withGhosts<N>(g, C, coarse, launch);
@@ -52,33 +43,19 @@ int doProlongLinear(te_gmg *g, int fine_level, const double *coarse, double *fin
 		HIPCHK(hipGetLastError());
 		return TE_OK;
 	}
-	switch (L.n) {
-		case 4: return prolongLinearN<4>(g, L, C, coarse, fine);
-		case 8: return prolongLinearN<8>(g, L, C, coarse, fine);
-		case 16: return prolongLinearN<16>(g, L, C, coarse, fine);
-		default: return prolongLinearN<32>(g, L, C, coarse, fine);
-	}
+	return dispatchN(L.n, [&](auto n) { return prolongLinearN<decltype(n)::value>(g, L, C, coarse, fine); });
 }
 
 // ---- the quadratic FMG interpolation (te_prolong_quadratic): fine = Pi coarse
 template <int N> static int prolongQuadraticN(te_gmg *g, LevelHost &L, LevelHost &C, const double *coarse, double *fine)
 {
-	const int zs     = projSlabs<N>(g, L.P);
+	const int zs     = stencilSlabs<N>(g, L.P);
 	auto      launch = [&](LevelDev D) {
-        Timed      t(g, KC_PROLONG_QUADRATIC, (size_t) L.P * L.nc);
-        const dim3 grid(8 * ((L.P * zs + 7) / 8)), blk(Tile3<N>::TPB);
-        switch (zs) {
-            case 1: hipLaunchKernelGGL((k_prolong_quadratic3d<N, 1>), grid, blk, 0, g->stream, L.P, D, L.parent.p, L.orth.p, coarse, fine); break;
-            case 2:
-                if constexpr (N >= 8) hipLaunchKernelGGL((k_prolong_quadratic3d<N, 2>), grid, blk, 0, g->stream, L.P, D, L.parent.p, L.orth.p, coarse, fine);
-                break;
-            case 8:
-                if constexpr (N >= 32) hipLaunchKernelGGL((k_prolong_quadratic3d<N, 8>), grid, blk, 0, g->stream, L.P, D, L.parent.p, L.orth.p, coarse, fine);
-                break;
-            default:
-                if constexpr (N >= 16) hipLaunchKernelGGL((k_prolong_quadratic3d<N, 4>), grid, blk, 0, g->stream, L.P, D, L.parent.p, L.orth.p, coarse, fine);
-                break;
-        }
+		Timed t(g, KC_PROLONG_QUADRATIC, (size_t) L.P * L.nc);
+		dispatchSlabs<N>(zs, [&](auto z) {
+			hipLaunchKernelGGL((k_prolong_quadratic3d<N, decltype(z)::value>), slabGrid(L.P, zs), dim3(Tile3<N>::TPB), 0, g->stream, L.P, D, L.parent.p,
+			                   L.orth.p, coarse, fine);
+		});
 	};
 	int rc = withGhosts<N>(g, C, coarse, launch);
 	if (rc) return rc;
@@ -102,12 +79,7 @@ int doProlongQuadratic(te_gmg *g, int fine_level, const double *coarse, double *
 		HIPCHK(hipGetLastError());
 		return TE_OK;
 	}
-	switch (L.n) {
-		case 4: return prolongQuadraticN<4>(g, L, C, coarse, fine);
-		case 8: return prolongQuadraticN<8>(g, L, C, coarse, fine);
-		case 16: return prolongQuadraticN<16>(g, L, C, coarse, fine);
-		default: return prolongQuadraticN<32>(g, L, C, coarse, fine);
-	}
+	return dispatchN(L.n, [&](auto n) { return prolongQuadraticN<decltype(n)::value>(g, L, C, coarse, fine); });
 }
 } // namespace tei
 

@@ -26,42 +26,22 @@ static RegridWs &regridWs(te_gmg *g)
 
 template <int N> static void indicatorN(te_gmg *g, LevelHost &L, const double *u, RegridWs &W)
 {
-	const int zs = projSlabs<N>(g, L.P);
+	const int zs = stencilSlabs<N>(g, L.P);
 	Timed     t(g, KC_INDICATOR, (size_t) L.P * L.nc);
 	double   *first = zs == 1 ? W.out.p : W.part.p;
-	const dim3 grid(L.P * zs), blk(256);
-	switch (zs) {
-		case 1: hipLaunchKernelGGL((k_indicator3d<N, 1>), grid, blk, 0, g->stream, L.P, u, first); break;
-		case 2:
-			if constexpr (N >= 8) hipLaunchKernelGGL((k_indicator3d<N, 2>), grid, blk, 0, g->stream, L.P, u, first);
-			break;
-		case 8:
-			if constexpr (N >= 32) hipLaunchKernelGGL((k_indicator3d<N, 8>), grid, blk, 0, g->stream, L.P, u, first);
-			break;
-		default:
-			if constexpr (N >= 16) hipLaunchKernelGGL((k_indicator3d<N, 4>), grid, blk, 0, g->stream, L.P, u, first);
-			break;
-	}
+	dispatchSlabs<N>(zs, [&](auto z) {
+		hipLaunchKernelGGL((k_indicator3d<N, decltype(z)::value>), dim3(L.P * zs), dim3(256), 0, g->stream, L.P, u, first);
+	});
 	if (zs > 1) hipLaunchKernelGGL(k_indicator_final, dim3((L.P + 255) / 256), dim3(256), 0, g->stream, L.P, zs, W.part.p, W.out.p);
 }
 
 template <int N> static void regridN(te_gmg *g, LevelHost &L, const int32_t *map, const double *src, double *dst)
 {
-	const int  zs = projSlabs<N>(g, L.P);
-	Timed      t(g, KC_REGRID, (size_t) L.P * L.nc);
-	const dim3 grid(8 * ((L.P * zs + 7) / 8)), blk(Tile3<N>::TPB);
-	switch (zs) {
-		case 1: hipLaunchKernelGGL((k_regrid3d<N, 1>), grid, blk, 0, g->stream, L.P, map, src, dst); break;
-		case 2:
-			if constexpr (N >= 8) hipLaunchKernelGGL((k_regrid3d<N, 2>), grid, blk, 0, g->stream, L.P, map, src, dst);
-			break;
-		case 8:
-			if constexpr (N >= 32) hipLaunchKernelGGL((k_regrid3d<N, 8>), grid, blk, 0, g->stream, L.P, map, src, dst);
-			break;
-		default:
-			if constexpr (N >= 16) hipLaunchKernelGGL((k_regrid3d<N, 4>), grid, blk, 0, g->stream, L.P, map, src, dst);
-			break;
-	}
+	const int zs = stencilSlabs<N>(g, L.P);
+	Timed     t(g, KC_REGRID, (size_t) L.P * L.nc);
+	dispatchSlabs<N>(zs, [&](auto z) {
+		hipLaunchKernelGGL((k_regrid3d<N, decltype(z)::value>), slabGrid(L.P, zs), dim3(Tile3<N>::TPB), 0, g->stream, L.P, map, src, dst);
+	});
 }
 
 // One row per destination patch from the two solvers' leaf tables. A match by node id is confirmed by position and size: ids are
@@ -140,12 +120,7 @@ int te_patch_indicator(te_gmg *g, int level, const te_vec *u, double *out_host)
 			Timed t(g, KC_INDICATOR, (size_t) L.P * L.nc);
 			hipLaunchKernelGGL(k_indicator2d, dim3(L.P), dim3(256), 0, g->stream, L.n, L.P, u->d, W.out.p);
 		} else {
-			switch (L.n) {
-				case 4: indicatorN<4>(g, L, u->d, W); break;
-				case 8: indicatorN<8>(g, L, u->d, W); break;
-				case 16: indicatorN<16>(g, L, u->d, W); break;
-				default: indicatorN<32>(g, L, u->d, W); break;
-			}
+			dispatchN(L.n, [&](auto n) { indicatorN<decltype(n)::value>(g, L, u->d, W); });
 		}
 		HIPCHK(hipGetLastError());
 		HIPCHK(hipStreamSynchronize(g->stream));
@@ -183,12 +158,7 @@ int te_vec_regrid(te_gmg *src, const te_vec *u_src, te_gmg *dst, te_vec *u_dst)
 			hipLaunchKernelGGL(k_regrid2d, dim3(gridFor((size_t) L.P * L.nc / 2, 256, 65536)), dim3(256), 0, dst->stream, L.n, L.P, W.map.p, u_src->d,
 			                   u_dst->d);
 		} else {
-			switch (L.n) {
-				case 4: regridN<4>(dst, L, W.map.p, u_src->d, u_dst->d); break;
-				case 8: regridN<8>(dst, L, W.map.p, u_src->d, u_dst->d); break;
-				case 16: regridN<16>(dst, L, W.map.p, u_src->d, u_dst->d); break;
-				default: regridN<32>(dst, L, W.map.p, u_src->d, u_dst->d); break;
-			}
+			dispatchN(L.n, [&](auto n) { regridN<decltype(n)::value>(dst, L, W.map.p, u_src->d, u_dst->d); });
 		}
 		HIPCHK(hipGetLastError());
 		return TE_OK;

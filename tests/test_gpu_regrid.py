@@ -17,7 +17,7 @@ from tests import regrid_util as ru, util
 pytestmark = pytest.mark.gpu
 
 # (mesh, n, divides, dim): the smallest patch, a z-slab size with several blocks, the production patch size (8 -> 64 patches of 32^3:
-# eight slabs per patch by projSlabs), coarse/fine trees at a four-slab size and five levels deep, the 2D kernel on a tree and at
+# eight slabs per patch by stencilSlabs), coarse/fine trees at a four-slab size and five levels deep, the 2D kernel on a tree and at
 # 64^2. One slab per patch needs 2048 patches or more: test_one_slab_per_patch below.
 SHAPES = [("uniform", 4, 2, 3), ("uniform", 8, 2, 3), ("uniform", 32, 1, 3), ("2refine.bin", 16, 0, 3), ("multi_refine.bin", 8, 0, 3),
           ("2d2ref.bin", 4, 0, 2), ("uniform", 64, 2, 2)]
@@ -128,7 +128,7 @@ def test_transfer(case, pattern):
 
 @pytest.mark.parametrize("n", [8, 16])
 def test_one_slab_per_patch(n):
-    """4096 patches: projSlabs gives one slab per patch, the instantiations a production-size level runs (k_regrid3d<N, 1>,
+    """4096 patches: stencilSlabs gives one slab per patch, the instantiations a production-size level runs (k_regrid3d<N, 1>,
     k_indicator3d<N, 1>). The mixed pattern: 8 refined patches, one coarsened, the rest copied."""
     m = util.mesh("uniform", 4, 3)
     m2 = m.adapt(ru.mixed_flags(m))
