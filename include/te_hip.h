@@ -364,6 +364,40 @@ int te_patch_indicator(te_gmg *g, int level, const te_vec *u, double *out_host);
  * level or solver, different n / dim / device, or a destination leaf that has no source under the three cases above -- the message
  * names its node id. */
 int te_vec_regrid(te_gmg *src, const te_vec *u_src, te_gmg *dst, te_vec *u_dst);
+/* te_faces_regrid: U_dst = the transfer of the FACE vector U_src (te_vec_create_faces) from src's mesh to dst's mesh, so that a
+ * projected MAC velocity travels with the pressure: what te_divergence gives on dst is what it gave on src, cell by cell on copied
+ * patches, on every fine cell of a refined patch the value of its coarse cell, on a coarsened patch the mean over the 2^dim fine
+ * cells. Conditions as for te_vec_regrid: level-0 face vectors of their solvers, the same dim, n and device, single rank, meshes one
+ * te_mesh_adapt apart (or the same); runs on dst's stream after a synchronisation of src's stream; U_src is not modified; neither
+ * solver's state changes (a te_vcycle afterwards gives the bits it gave before). The map of destination leaves is te_vec_regrid's.
+ * Notation: patch X has n cells per axis and spacings h_a; F_a(i; t) is component a on face plane i = 0 .. n along a at the tangential
+ * cell indices t: LO_a[cell with index i along a] for i < n, HI_a[t] for i = n. Every LO_a and HI_a block of every destination patch is
+ * written, by exactly one writer per entry, without atomics.
+ *   copy     L is a source leaf: the source patch's dim n^dim + dim n^(dim-1) doubles, bit for bit.
+ *   coarsen  L is the tree parent of 2^dim source leaves. Coarse face (a, I, t) is the mean of the 2^(dim-1) fine faces that cover it,
+ *            in the child with orthant bits o_a = (I >= n/2), o_b = (t_b >= n/2) -- the mid-plane I = n/2 is the upper child's plane 0
+ *            -- at fine plane 2I - o_a n and fine tangential indices 2 t_b - o_b n + {0, 1}. 3D: ((p00 + p10) + (p01 + p11)) * 0.25 with
+ *            the first index along the lower remaining axis; 2D: (p0 + p1) * 0.5 (te_boundary_restrict's associations).
+ *   refine   L's tree parent is a source leaf X, L its orthant o. Second order; EVERY patch edge is treated one-sidedly, neighbour or
+ *            not, so no ghost of the source hierarchy is read. For b != a the tangential slope is
+ *              s_ab(i; t) = (F_a(i; t + e_b) - F_a(i; t - e_b)) * 0.125,
+ *            F_a extended along b by F(-1) = 3 F(0) - 3 F(1) + F(2) and F(n) = 3 F(n-1) - 3 F(n-2) + F(n-3). Fine plane i_f = 0 .. n and
+ *            fine tangential indices t_f of L map to X's doubled lattice: I = i_f + o_a n, T_b = t_b + o_b n, c_b = T_b >> 1,
+ *            sigma_b = -1 for T_b even and +1 for T_b odd. With
+ *              G_a(i; T) = F_a(i; c) + sum_{b != a, ascending} sigma_b s_ab(i; c)
+ *            the fine value is G_a(I / 2; T) for I even and, for I odd (the face lies inside coarse cell c, c_a = (I - 1) / 2),
+ *              0.5 (G_a(c_a; T) + G_a(c_a + 1; T)) + sum_{b != a, ascending} 0.5 (h_a / h_b) (s_ba(c_b + 1; c) - s_ba(c_b; c)):
+ *            the last term is the difference, between the coarse cell's upper and lower b-face, of component b's slope along a -- one
+ *            value per coarse cell and axis, shared by the cell's 2^(dim-1) interior a-faces; h_a / h_b from X's lengths.
+ *            Consequences: every fine cell's te_divergence equals its coarse cell's (to rounding); a field whose components are linear
+ *            in x, y, z is reproduced; a smooth field is transferred with second-order error; the two stored copies of a face shared
+ *            by two refined patches get the same bits when the source's copies agree (a face's value depends on data of its own
+ *            plane only, through the same expressions; FMA contraction is off in these kernels). Where a refined patch meets a coarser
+ *            one the two copies differ by construction, as for te_gradient.
+ * TE_ESTATE (the message says "sharded") when either hierarchy is sharded; TE_EINVAL for NULL, a vector that is not a face vector
+ * (domain, interface and boundary vectors are refused), a vector of another level or solver, the same vector as source and
+ * destination, different n / dim / device, or a destination leaf without a source -- the message names its node id. */
+int te_faces_regrid(te_gmg *src, const te_vec *U_src, te_gmg *dst, te_vec *U_dst);
 
 /* The TE_* switches (docs/SWITCHES.md) are read from the environment once, in te_gmg_create. This call sets (value) or
  * clears (NULL) one of them for this solver afterwards -- how the tests pin one implementation against another. TE_ESTATE

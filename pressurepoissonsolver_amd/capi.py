@@ -131,6 +131,7 @@ SYMBOLS = {
     "te_fmg": (_I, [_P, _P, _P, _P, _P, _I, _PD]),
     "te_patch_indicator": (_I, [_P, _I, _P, _P]),
     "te_vec_regrid": (_I, [_P, _P, _P, _P]),
+    "te_faces_regrid": (_I, [_P, _P, _P, _P]),
     "te_gmg_set_interpolator": (_I, [_P, _I]),
     "te_gmg_interpolator": (_I, [_P]),
     "te_vcycle": (_I, [_P, C.POINTER(CycleOpts), _P, _P]),
@@ -415,6 +416,12 @@ def regrid(src_g, u_src, dst_g, u_dst):
     """te_vec_regrid: u_dst (level 0 of dst_g) = u_src (level 0 of src_g) carried to dst_g's mesh, one te_mesh_adapt away:
     copy / quadratic refinement / AvgRstr coarsening per destination leaf"""
     check(lib().te_vec_regrid(src_g.h, u_src.h, dst_g.h, u_dst.h))
+
+
+def regrid_faces(src_g, U_src, dst_g, U_dst):
+    """te_faces_regrid: the face vector U_dst (level 0 of dst_g) = U_src (level 0 of src_g) carried to dst_g's mesh, one te_mesh_adapt
+    away: copy / divergence-preserving second-order refinement / face averages per destination leaf"""
+    check(lib().te_faces_regrid(src_g.h, U_src.h, dst_g.h, U_dst.h))
 
 
 def face_vector_size(n, dim):

@@ -14,6 +14,7 @@
 //   gmg_prolong.hip    the linear interpolator, the solver's choice of interpolator, the quadratic FMG interpolation (prolongkernels.hpp)
 //   gmg_fmg.hip        the full-multigrid solve te_fmg and its work vectors
 //   gmg_regrid.hip     the per-patch indicator te_patch_indicator and the transfer between two meshes te_vec_regrid (regridkernels.hpp)
+//   gmg_faceregrid.hip the transfer of a face vector between two meshes te_faces_regrid (faceregridkernels.hpp)
 #pragma once
 #include "capi_common.hpp"
 #include "level_tables.hpp"
@@ -94,7 +95,10 @@ enum KClass : int {
 	KC_PROLONG_QUADRATIC, KC_BOUNDARY_RESTRICT,
 	// regridding (regridkernels.hpp): the per-patch indicator (8 B per site) and the transfer between two meshes (16 B per copied
 	// site, about 9.4 per refined one, 72 per coarsened cell; cells = destination sites)
-	KC_INDICATOR, KC_REGRID, KC_COUNT
+	KC_INDICATOR, KC_REGRID,
+	// the transfer of a face vector (faceregridkernels.hpp): per destination site at 32^3 (a cell, its three lower faces
+	// and its share of the HI blocks: 24.75 B) 49.5 B copied, 24.75 written + about 4 read refined, 24.75 + 99 coarsened
+	KC_FACE_REGRID, KC_COUNT
 };
 extern const char *kclassName[KC_COUNT]; // (gmg_core.hip)
 
@@ -722,6 +726,7 @@ int doBoundaryRestrict(te_gmg *g, int fine_level, const double *fine_bdata, doub
 void fmgFree(te_gmg *g); // (te_gmg_release_workspace, te_gmg_destroy)
 // ---- gmg_regrid.hip
 void regridFree(te_gmg *g); // (te_gmg_destroy)
+int  regridMapUpload(te_gmg *src, te_gmg *dst, const char *who, const int32_t **map_dev); // one row per patch of dst, in dst's buffer
 // ---- gmg_launch2d.hip
 int prepareGhosts2d(te_gmg *g, LevelHost &L, const double *u);
 template <int MODE> int launchStencil2d(te_gmg *g, LevelHost &L, const double *u, const double *f, double *out, double omega, int redmode = RED_NONE,

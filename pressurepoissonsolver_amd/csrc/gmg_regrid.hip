@@ -46,7 +46,7 @@ template <int N> static void regridN(te_gmg *g, LevelHost &L, const int32_t *map
 
 // One row per destination patch from the two solvers' leaf tables. A match by node id is confirmed by position and size: ids are
 // reused once a node has been removed, so two meshes further apart than one adapt step could agree on an id and mean another box.
-static int regridMap(const te_gmg *src, const te_gmg *dst, std::vector<int32_t> &map)
+static int regridMap(const te_gmg *src, const te_gmg *dst, const char *who, std::vector<int32_t> &map)
 {
 	const int dim = dst->dim, north = 1 << dim, Pd = (int) dst->leaf_id.size(), Ps = (int) src->leaf_id.size();
 	std::map<int, int>              leaf;     // source node id -> source patch
@@ -96,10 +96,28 @@ static int regridMap(const te_gmg *src, const te_gmg *dst, std::vector<int32_t> 
 			}
 		}
 		if (!ok)
-			return te::fail(TE_EINVAL, "te_vec_regrid: destination leaf with node id " + std::to_string(id)
+			return te::fail(TE_EINVAL, std::string(who) + ": destination leaf with node id " + std::to_string(id)
 			                               + " has no source: it is neither a source leaf, nor the child of one, nor the parent of 2^dim source "
 			                                 "leaves in the same place (the two meshes must be one te_mesh_adapt apart)");
 	}
+	return TE_OK;
+}
+
+// the map of a transfer from src to dst on the device, in dst's buffer (te_vec_regrid and te_faces_regrid share it); both streams
+// are synchronised: src's, whose results the transfer reads, and dst's, where an earlier transfer may still read the map that is
+// replaced or overwritten here
+int regridMapUpload(te_gmg *src, te_gmg *dst, const char *who, const int32_t **map_dev)
+{
+	int                  rc;
+	std::vector<int32_t> map;
+	if ((rc = regridMap(src, dst, who, map))) return rc;
+	HIPCHK(hipSetDevice(dst->device));
+	HIPCHK(hipStreamSynchronize(src->stream));
+	RegridWs &W = regridWs(dst);
+	HIPCHK(hipStreamSynchronize(dst->stream));
+	if (W.map.n < map.size() && (rc = W.map.alloc(map.size()))) return rc;
+	HIPCHK(hipMemcpy(W.map.p, map.data(), sizeof(int32_t) * map.size(), hipMemcpyHostToDevice));
+	*map_dev = W.map.p;
 	return TE_OK;
 }
 } // namespace tei
@@ -144,21 +162,15 @@ int te_vec_regrid(te_gmg *src, const te_vec *u_src, te_gmg *dst, te_vec *u_dst)
 		if (u_src == u_dst) return te::fail(TE_EINVAL, "te_vec_regrid: source and destination are the same vector");
 		LevelHost &L = *dst->levels[0];
 		if (L.P == 0) return TE_OK;
-		std::vector<int32_t> map;
-		if ((rc = regridMap(src, dst, map))) return rc;
-		HIPCHK(hipSetDevice(dst->device));
-		HIPCHK(hipStreamSynchronize(src->stream));
-		RegridWs &W = regridWs(dst);
-		HIPCHK(hipStreamSynchronize(dst->stream)); // (an earlier transfer may still read the map that is replaced or overwritten next)
-		if (W.map.n < map.size() && (rc = W.map.alloc(map.size()))) return rc;
-		HIPCHK(hipMemcpy(W.map.p, map.data(), sizeof(int32_t) * map.size(), hipMemcpyHostToDevice));
+		const int32_t *map = nullptr;
+		if ((rc = regridMapUpload(src, dst, "te_vec_regrid", &map))) return rc;
 		if (L.xf_valid_for == u_dst->d) L.xf_valid_for = nullptr; // u_dst is overwritten
 		if (L.dim == 2) {
 			Timed t(dst, KC_REGRID, (size_t) L.P * L.nc);
-			hipLaunchKernelGGL(k_regrid2d, dim3(gridFor((size_t) L.P * L.nc / 2, 256, 65536)), dim3(256), 0, dst->stream, L.n, L.P, W.map.p, u_src->d,
+			hipLaunchKernelGGL(k_regrid2d, dim3(gridFor((size_t) L.P * L.nc / 2, 256, 65536)), dim3(256), 0, dst->stream, L.n, L.P, map, u_src->d,
 			                   u_dst->d);
 		} else {
-			dispatchN(L.n, [&](auto n) { regridN<decltype(n)::value>(dst, L, W.map.p, u_src->d, u_dst->d); });
+			dispatchN(L.n, [&](auto n) { regridN<decltype(n)::value>(dst, L, map, u_src->d, u_dst->d); });
 		}
 		HIPCHK(hipGetLastError());
 		return TE_OK;

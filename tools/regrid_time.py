@@ -1,7 +1,8 @@
 """Tooling: what a regrid costs on the device. Uniform meshes in 32^3 patches, destination of size^3 cells unless said otherwise, the
 three kinds of te_vec_regrid each on its own -- copy (size^3 -> the same mesh on a second solver), refine ((size/2)^3 -> size^3, every
 leaf refined), coarsen (size^3 -> (size/2)^3, every family coarsened) -- beside a flat te_vec_copy of a size^3 vector and
-te_patch_indicator on size^3, alternating in one process, REPS repetitions after a warm-up round. Kernel times from the library's
+te_patch_indicator on size^3, and the same three kinds of te_faces_regrid on face vectors (filled by te_gradient of the random vector),
+alternating in one process, REPS repetitions after a warm-up round. Kernel times from the library's
 profile rows (HIP events around each launch); the indicator's wall time includes its synchronisation and the copy of one double per
 patch to the host. Writes profiles/regrid.json.
 
@@ -23,6 +24,10 @@ N = 32
 # algorithmic bytes per DESTINATION site: copy reads and writes a value; refine writes one, reads 1/8 of a source value plus the ring
 # of the octant ((18^3 - 16^3) / 32^3 values); coarsen writes one and reads eight
 BYTES = dict(copy=16.0, refine=8 + 8 * 18 ** 3 / N ** 3, coarsen=72.0, flat_copy=16.0, indicator=8.0)
+# te_faces_regrid, per destination site = a cell with its three lower faces and its share of the HI blocks (24 + 24/32 B): copy reads and
+# writes that; refine writes it and reads, per component, the octant's block of 17 x 18 x 18 values; coarsen reads four fine faces per face
+FACE = 24.0 + 24.0 / N
+BYTES.update(faces_copy=2 * FACE, faces_refine=FACE + 3 * 8 * 17 * 18 * 18 / N ** 3, faces_coarsen=5 * FACE)
 
 
 def solver(divides):
@@ -57,8 +62,25 @@ def run(size):
     assert u_half.checksumLocal() == r.checksumLocal(), "coarsen differs from te_restrict"
     u_half.copy(keep)
     capi.regrid(g_half, u_half, g, v)
-    assert np.isfinite(v.infNorm()) and v.infNorm() <= 1.75 ** 3 * u_half.infNorm(), "refine is out of its bound"
+    # (per axis the weights' absolute sum is at most (30 + 5 * 7 + 3) / 32: an extrapolated ghost, weight 3 + 3 + 1, under the 5/32 tap)
+    assert np.isfinite(v.infNorm()) and v.infNorm() <= 2.125 ** 3 * u_half.infNorm(), "refine is out of its bound"
     del r, keep
+    # face vectors: the gradients of the random vectors; a copy has the source's checksum, and refining keeps the divergence of
+    # every cell (so its maximum) to rounding
+    U, V, U_same, U_half = g.new_face_vector(0), g.new_face_vector(0), g_same.new_face_vector(0), g_half.new_face_vector(0)
+    g.gradient(u, U)
+    g_half.gradient(u_half, U_half)
+    capi.regrid_faces(g, U, g_same, U_same)
+    assert U_same.checksumLocal() == U.checksumLocal(), "face copy differs from its source"
+    capi.regrid_faces(g_half, U_half, g, V)
+    d, d_half = g.new_vector(0), g_half.new_vector(0)
+    g.divergence(V, d)
+    g_half.divergence(U_half, d_half)
+    assert abs(d.infNorm() - d_half.infNorm()) <= 1e-9 * d_half.infNorm(), "face refinement changed the divergence"
+    del d, d_half
+    ops.update(faces_copy=(g_same, lambda: capi.regrid_faces(g, U, g_same, U_same), "regrid_faces", H.cells(0)),
+               faces_refine=(g, lambda: capi.regrid_faces(g_half, U_half, g, V), "regrid_faces", H.cells(0)),
+               faces_coarsen=(g_half, lambda: capi.regrid_faces(g, U, g_half, U_half), "regrid_faces", H_half.cells(0)))
     out = dict(size=size, n=N, patches=H.sizes(0)[1], reps=REPS, kinds={})
     for name, (gg, fn, row, sites) in ops.items():
         for _ in range(3):
@@ -79,7 +101,7 @@ def run(size):
         out["kinds"][name] = dict(kernel_ms=round(ms, 4), wall_ms_per_call=round(wall, 4), destination_sites=sites, bytes_per_site=round(BYTES[name], 3),
                                   tb_per_s=round(BYTES[name] * sites / (ms * 1e-3) / 1e12, 3))
     flat = out["kinds"]["flat_copy"]["kernel_ms"]
-    for name in ("copy", "refine", "coarsen"):
+    for name in ("copy", "refine", "coarsen", "faces_copy", "faces_refine", "faces_coarsen"):
         k = out["kinds"][name]
         k["ratio_to_flat_copy_per_byte"] = round((k["kernel_ms"] / (k["bytes_per_site"] * k["destination_sites"])) / (flat / (16.0 * H.cells(0))), 3)
     print(f"{size}^3: " + "; ".join(f"{k}: {v['kernel_ms']:.3f} ms ({v['tb_per_s']:.2f} TB/s)" for k, v in out["kinds"].items()), flush=True)
@@ -92,7 +114,7 @@ def main():
     if args and args[0] == "--out":
         path, args = os.path.abspath(args[1]), args[2:]
     sizes = [int(a) for a in args] or [256, 512]
-    result = dict(tool="tools/regrid_time.py", setup="uniform meshes, 32^3 patches; te_vec_regrid per kind, te_vec_copy, te_patch_indicator", runs=[run(s) for s in sizes])
+    result = dict(tool="tools/regrid_time.py", setup="uniform meshes, 32^3 patches; te_vec_regrid and te_faces_regrid per kind, te_vec_copy, te_patch_indicator", runs=[run(s) for s in sizes])
     os.makedirs(os.path.dirname(path), exist_ok=True)
     with open(path, "w") as fh:
         json.dump(result, fh, indent=1)
