@@ -3,7 +3,7 @@
 
 namespace tei
 {
-int smoothOnce(te_gmg *g, int level, const te_vec *f, te_vec *u, int smoother, double omega, bool zero_guess = false)
+int smoothOnce(te_gmg *g, int level, const te_vec *f, te_vec *u, int smoother, double omega, bool zero_guess = false, bool faces_only = false)
 {
 	LevelHost &L = *g->levels[level];
 	int        rc;
@@ -11,7 +11,7 @@ int smoothOnce(te_gmg *g, int level, const te_vec *f, te_vec *u, int smoother, d
 	switch (smoother) {
 		case TE_SMOOTH_PATCH_SOLVE: { // keeps xf_valid_for itself
 			bool swapped = false;
-			rc           = patchSolve(g, L, f->d, u->d, zero_guess, nullptr, &swapped);
+			rc           = patchSolve(g, L, f->d, u->d, {zero_guess, nullptr, faces_only}, &swapped);
 			if (rc == TE_OK && swapped) swapData(u, L.t.get()); // (2D: out of place)
 			return rc;
 		}
@@ -35,6 +35,23 @@ int smoothOnce(te_gmg *g, int level, const te_vec *f, te_vec *u, int smoother, d
 	}
 }
 
+// Around a visit() from outside: what the levels say about compact x faces and face-layer iterates belongs to one cycle. It starts
+// empty and is dropped when the cycle ends, also when it ends in an exception (guarded() turns that into an error code).
+struct CycleScope {
+	te_gmg *g;
+	void    forget() const { for (auto &L : g->levels) L->xf_valid_for = nullptr, L->ps_faces = false; }
+	explicit CycleScope(te_gmg *g_) : g(g_)
+	{
+		forget();
+		g->in_cycle = !g->cfg.has(O_NO_XF);
+	}
+	~CycleScope()
+	{
+		g->in_cycle = false;
+		forget();
+	}
+};
+
 // GMG/VCycle.h:44-62, GMG/WCycle.h:45-68, GMG/Cycle.h:56-90.
 // `u_zero`: u is logically zero on entry but has NOT been written yet (fused mode): the first RB-GS
 // sweep then runs its zero-guess variant and the 8 B/site zero-fill never happens; any other first
@@ -48,7 +65,7 @@ int visit(te_gmg *g, const te_cycle_opts *o, int l, const te_vec *f, te_vec *u, 
 	g->cur_level        = l;
 	// The one predicate for every fused form below that has DrctIntp's arithmetic baked in: the sweeps on u + P e (pending_prolong),
 	// the unstored iterate of fuse = 3 with the ghost terms exported for it (fcorr) and the pre-sweep that keeps only face layers
-	// (ps_faces_req), the 2D folds. With the linear interpolator they are off: the iterate is stored, te_prolong_linear_add's kernel
+	// (PatchSolveOpts::faces_only), the 2D folds. With the linear interpolator they are off: the iterate is stored, te_prolong_linear_add's kernel
 	// prolongs, plain post-sweeps follow. The restriction-side fusions do not depend on the interpolator and stay.
 	const bool drct = g->interp == TE_INTERP_DIRECT;
 	const double *fcorr_in = (L.f_has_corr && L.fcorr.p) ? L.fcorr.p : nullptr; // ghost terms that still belong to f (see below)
@@ -97,11 +114,8 @@ int visit(te_gmg *g, const te_cycle_opts *o, int l, const te_vec *f, te_vec *u, 
 				pending_prolong = nullptr;
 				const bool last = final_call && i == sweeps - 1 && !(l == 0 && g->keep_final_xf);
 				if (sm == TE_SMOOTH_PATCH_SOLVE) { // reads u + P c on the face layers only, then overwrites u
-					bool swapped    = false;
-					g->no_xf_export = last;
-					r               = patchSolve(g, L, f->d, u->d, false, c, &swapped);
-					g->no_xf_export = false;
-					if (r) return r;
+					bool swapped = false;
+					if ((r = patchSolve(g, L, f->d, u->d, {false, c, false, !last}, &swapped))) return r;
 					if (swapped) swapData(u, L.t.get()); // (2D: out of place)
 					continue;
 				}
@@ -228,10 +242,10 @@ int visit(te_gmg *g, const te_cycle_opts *o, int l, const te_vec *f, te_vec *u, 
 		u_zero = false;
 		// opts.fuse = 3: ... and so does everything the post-sweep reads of this iterate (its interface terms, k_face_corr3d
 		// on u + P e): the pre-sweep stores the six face layers of its result and nothing else (bit-identical; rank-local)
-		L.ps_faces_req = drct && o->fuse >= 3 && o->cycle_type == 0 && o->post_sweeps >= 1 && L.n == 32 && L.P_global >= 256 && L.prolong_fusable
-		                 && (L.sym_ok || L.n_pure == L.P) && L.f6buf.p && !g->cfg.has(O_PS_SLOW) && !g->cfg.has(O_PS_MODE)
-		                 && !g->cfg.has(O_NO_PS_FACES);
-		if ((rc = smoothOnce(g, l, f, u, TE_SMOOTH_PATCH_SOLVE, o->omega, true))) return rc;
+		const bool faces_only = drct && o->fuse >= 3 && o->cycle_type == 0 && o->post_sweeps >= 1 && L.n == 32 && L.P_global >= 256 && L.prolong_fusable
+		                        && (L.sym_ok || L.n_pure == L.P) && L.f6buf.p && !g->cfg.has(O_PS_SLOW) && !g->cfg.has(O_PS_MODE)
+		                        && !g->cfg.has(O_NO_PS_FACES);
+		if ((rc = smoothOnce(g, l, f, u, TE_SMOOTH_PATCH_SOLVE, o->omega, true, faces_only))) return rc;
 		if ((rc = interfaceResidRestrict(g, L, u->d, xfFor(L, u->d), C.f->d, C.f->n))) return rc;
 		have_coarse_f = true;
 	} else if (o->fuse >= 2 && u_zero && o->pre_sweeps == 1 && o->smoother == TE_SMOOTH_PATCH_SOLVE && ps2dResidFusable(g, L) && !fold_in.fine) {
@@ -284,11 +298,10 @@ static int verifySchedule(te_gmg *g, const te_cycle_opts *o)
 	g->profiling    = false;
 	g->recording    = true;
 	g->record.clear();
-	for (auto &L : g->levels) L->xf_valid_for = nullptr;
-	g->in_cycle = !g->cfg.has(O_NO_XF);
-	rc          = visit(g, o, 0, f, u, o->fuse != 0);
-	g->in_cycle = false;
-	for (auto &L : g->levels) L->xf_valid_for = nullptr;
+	{
+		CycleScope in(g);
+		rc = visit(g, o, 0, f, u, o->fuse != 0);
+	}
 	g->recording = false;
 	g->profiling = prof;
 	(void) hipStreamSynchronize(g->stream);
@@ -402,14 +415,14 @@ int vcycleWith(te_gmg *g, const te_cycle_opts *o, const te_vec *f, te_vec *u, co
 		g->verified_opts.insert(optsKey(o));
 	}
 	if (!o->fuse && (rc = te_vec_set(u, 0.0))) return rc; // Cycle.h:118
-	for (auto &L : g->levels) L->xf_valid_for = nullptr, L->ps_faces = L->ps_faces_req = false;
-	g->in_cycle    = !g->cfg.has(O_NO_XF);
-	g->pending_rhs = pending;
-	rc             = visit(g, o, 0, f, u, o->fuse != 0);
-	g->pending_rhs = nullptr;
-	g->in_cycle    = false;
-	const double *keep = (g->keep_final_xf && rc == TE_OK) ? g->levels[0]->xf_valid_for : nullptr; // (describes u->d, or nothing)
-	for (auto &L : g->levels) L->xf_valid_for = nullptr, L->ps_faces = L->ps_faces_req = false;
+	const double *keep;
+	{
+		CycleScope in(g);
+		g->pending_rhs = pending;
+		rc             = visit(g, o, 0, f, u, o->fuse != 0);
+		g->pending_rhs = nullptr;
+		keep           = (g->keep_final_xf && rc == TE_OK) ? g->levels[0]->xf_valid_for : nullptr; // (describes u->d, or nothing)
+	}
 	if (keep == u->d) g->levels[0]->xf_valid_for = keep;
 	return rc;
 	}
@@ -422,11 +435,8 @@ int cycleFrom(te_gmg *g, const te_cycle_opts *o, int l, const te_vec *f, te_vec 
 {
 	int rc;
 	if (!o->fuse && (rc = te_vec_set(u, 0.0))) return rc; // Cycle.h:118
-	for (auto &L : g->levels) L->xf_valid_for = nullptr, L->ps_faces = L->ps_faces_req = false;
-	g->in_cycle = !g->cfg.has(O_NO_XF);
-	rc          = visit(g, o, l, f, u, o->fuse != 0);
-	g->in_cycle = false;
-	for (auto &L : g->levels) L->xf_valid_for = nullptr, L->ps_faces = L->ps_faces_req = false;
+	CycleScope in(g);
+	rc           = visit(g, o, l, f, u, o->fuse != 0);
 	g->cur_level = 0;
 	return rc;
 }
@@ -749,11 +759,7 @@ int te_patch_apply(te_gmg *g, int level, const te_vec *u, te_vec *f)
 		int rc;
 		if ((rc = checkLevelVec(g, level, u, "te_patch_apply")) || (rc = checkLevelVec(g, level, f, "te_patch_apply"))) return rc;
 		if (u == f) return te::fail(TE_EINVAL, "te_patch_apply: in-place apply is not supported");
-		LevelHost &L  = *g->levels[level];
-		L.patch_local = true;
-		rc            = launchStencil<MODE_APPLY>(g, L, u->d, nullptr, f->d, 0.0);
-		L.patch_local = false;
-		return rc;
+		return launchStencil<MODE_APPLY>(g, *g->levels[level], u->d, nullptr, f->d, 0.0, RestrictDst(), nullptr, RED_NONE, nullptr, nullptr, true);
 	});
 }
 

@@ -67,10 +67,7 @@ int zeroSweepResidN(te_gmg *g, LevelHost &L, const double *f, double *out, doubl
 		}
 	}
 	// the new face layers of neighbours on other ranks (no-op on one rank)
-	L.pack_f6 = store_u ? nullptr : L.f6buf.p;
-	rc        = prepareGhosts<N>(g, L, out);
-	L.pack_f6 = nullptr;
-	if (rc) return rc;
+	if ((rc = prepareGhosts<N>(g, L, {out, store_u ? nullptr : L.f6buf.p}))) return rc;
 	L.ghost_has_v = !store_u; // (the slots of neighbours on other ranks hold their face layers of v until the next exchange of the level)
 	if (fcorr_out) { // the ghost terms were formed by the patches that own the face values: sort them into the coarse
 		// level's side array (a permutation copy of 6/128 of a vector instead of the fix-up pass)
@@ -138,7 +135,7 @@ int resweepProlongN(te_gmg *g, LevelHost &L, const double *f, double *out, const
 			// non-temporal stores)
 			const char *ve    = g->cfg.str(O_RESWEEP_V);
 			const bool  small = (size_t) L.P * L.nc * sizeof(double) <= ((size_t) 160 << 20);
-			const int   v     = ve ? atoi(ve) : (fcorr_in ? 3 : (g->cur_level != 0 ? 27 : (small ? 19 : 59)));
+			const int   v     = ve ? atoi(ve) : (fcorr_in ? 3 : (L.index != 0 ? 27 : (small ? 19 : 59)));
 			if (L.ncf > 0 || L.has_copy) { // refined level: copy-through patches / coarse-fine ghost slots
 				if (v == 3)
 					launchT(t, (k_rbgs_resweep_prolong3d<N, 3, false, true>), grid, blk, 0, g->stream, D, f, out, ps);
@@ -193,9 +190,8 @@ int resweepProlongN(te_gmg *g, LevelHost &L, const double *f, double *out, const
 		HIPCHK(hipGetLastError());
 		return TE_OK;
 	}
-	L.pack_f6 = L.f6buf.p; // neighbours on other ranks receive the face layers of v + P(coarse)
-	int rc    = withGhosts<N>(g, L, out /* unused: the faces come from pack_f6 */, launch, nullptr, xf_out, &ps);
-	L.pack_f6 = nullptr;
+	// neighbours on other ranks receive the face layers of v + P(coarse)
+	int rc = withGhosts<N>(g, L, {nullptr, L.f6buf.p, &ps}, launch, nullptr, xf_out);
 	if (rc) return rc;
 	HIPCHK(hipGetLastError());
 	return TE_OK;
@@ -218,10 +214,7 @@ template <int N> int interfaceResidRestrictN(te_gmg *g, LevelHost &L, const doub
 {
 	RestrictDst rd = restrictDst(L, coarse);
 	int rc;
-	L.pack_f6 = L.ps_faces ? L.f6buf.p : nullptr; // (the iterate exists only as its face layers)
-	rc        = prepareGhosts<N>(g, L, u);
-	L.pack_f6 = nullptr;
-	if (rc) return rc;
+	if ((rc = prepareGhosts<N>(g, L, {u, L.ps_faces ? L.f6buf.p : nullptr}))) return rc;
 	{
 		Timed t(g, KC_VECOP, coarse_n);
 		// (blocks exchanged in place: only this rank's run -- the others' runs are received, and with the direct-store transport a

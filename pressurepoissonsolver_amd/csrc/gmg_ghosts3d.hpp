@@ -8,13 +8,18 @@
 
 namespace tei
 {
-// make every ghost plane of `u` current: remote same-level faces (pack -> exchange -> ghost slots
+struct GhostSrc { // the iterate whose faces one ghost update reads
+	const double     *u;            // the stored iterate
+	const double     *f6 = nullptr; // non-null: the iterate exists only as its six face layers, there (LevelHost::f6buf)
+	const ProlongSrc *ps = nullptr; // the faces are those of the iterate + P(ps->coarse), which is never stored
+};
+
+// make every ghost plane of `src` current: remote same-level faces (pack -> exchange -> ghost slots
 // [0, nremote)), then the coarse/fine planes. Replaces SchurHelper.h:145-150 updateInterfaceDist.
-// `ps`: the iterate is u + P(ps->coarse) (never stored): the faces are packed with the correction added.
 // may_push: the exchange that follows is on the solver stream -- with the direct-store transport the pack kernel then stores the
 // layers into the receivers' ghost slots itself and raises their flags (PackPush); returns true when it did (the caller finishes
 // with pushFinish instead of an exchange of the send buffer)
-template <int N> bool packFaces(te_gmg *g, LevelHost &L, const double *u, const ProlongSrc *ps, bool may_push = false)
+template <int N> bool packFaces(te_gmg *g, LevelHost &L, const GhostSrc &src, bool may_push = false)
 {
 	const bool push = may_push && g->push.on && L.push_faces && !g->recording && L.push_face_dst[0].p;
 	Timed      t(g, push ? KC_EXCHANGE : KC_PACK, (size_t) L.nremote * L.nf);
@@ -31,45 +36,45 @@ template <int N> bool packFaces(te_gmg *g, LevelHost &L, const double *u, const 
 		pp.err    = g->push.err;
 		pp.err_host = g->push.err_host;
 	}
-	if (L.pack_f6) { // the iterate exists only as its face layers
+	if (src.f6) {
 		ProlongSrc none{nullptr, nullptr, nullptr};
-		hipLaunchKernelGGL(k_pack_faces6_3d<N>, grid, blk, 0, g->stream, L.send_faces.p, L.pack_f6, ps ? *ps : none, L.sendbuf.p, L.f6Off(), pp);
-	} else if (ps)
-		hipLaunchKernelGGL(k_pack_faces_prolong3d<N>, grid, blk, 0, g->stream, L.send_faces.p, u, *ps, L.sendbuf.p, pp);
+		hipLaunchKernelGGL(k_pack_faces6_3d<N>, grid, blk, 0, g->stream, L.send_faces.p, src.f6, src.ps ? *src.ps : none, L.sendbuf.p, L.f6Off(), pp);
+	} else if (src.ps)
+		hipLaunchKernelGGL(k_pack_faces_prolong3d<N>, grid, blk, 0, g->stream, L.send_faces.p, src.u, *src.ps, L.sendbuf.p, pp);
 	else
-		hipLaunchKernelGGL(k_pack_faces3d<N>, grid, blk, 0, g->stream, L.send_faces.p, u, L.sendbuf.p, pp);
+		hipLaunchKernelGGL(k_pack_faces3d<N>, grid, blk, 0, g->stream, L.send_faces.p, src.u, L.sendbuf.p, pp);
 	return push;
 }
 
-// ghost planes of the coarse/fine faces from the current iterate (u, or its face layers L.pack_f6 when it was never stored)
-template <int N> void cfGhosts(te_gmg *g, LevelHost &L, const double *u, const ProlongSrc *ps)
+// ghost planes of the coarse/fine faces from the current iterate
+template <int N> void cfGhosts(te_gmg *g, LevelHost &L, const GhostSrc &src)
 {
 	Timed      t(g, KC_CFGHOST, (size_t) L.ncf * L.nf);
 	const dim3 grid(L.ncf), blk(N * N < 256 ? N * N : 256);
-	if (L.pack_f6) {
-		if (ps)
-			hipLaunchKernelGGL((k_cf_ghost6_3d<N, true>), grid, blk, 0, g->stream, L.cf_desc.p, L.cf_slots.p, L.pack_f6, *ps, L.ghostCur(), L.f6Off());
+	if (src.f6) {
+		if (src.ps)
+			hipLaunchKernelGGL((k_cf_ghost6_3d<N, true>), grid, blk, 0, g->stream, L.cf_desc.p, L.cf_slots.p, src.f6, *src.ps, L.ghostCur(), L.f6Off());
 		else
-			hipLaunchKernelGGL((k_cf_ghost6_3d<N, false>), grid, blk, 0, g->stream, L.cf_desc.p, L.cf_slots.p, L.pack_f6, ProlongSrc(), L.ghostCur(), L.f6Off());
-	} else if (ps)
-		hipLaunchKernelGGL(k_cf_ghost_prolong3d<N>, grid, blk, 0, g->stream, L.cf_desc.p, L.cf_slots.p, u, *ps, L.ghostCur());
+			hipLaunchKernelGGL((k_cf_ghost6_3d<N, false>), grid, blk, 0, g->stream, L.cf_desc.p, L.cf_slots.p, src.f6, ProlongSrc(), L.ghostCur(), L.f6Off());
+	} else if (src.ps)
+		hipLaunchKernelGGL(k_cf_ghost_prolong3d<N>, grid, blk, 0, g->stream, L.cf_desc.p, L.cf_slots.p, src.u, *src.ps, L.ghostCur());
 	else
-		hipLaunchKernelGGL(k_cf_ghost3d<N>, grid, blk, 0, g->stream, L.cf_desc.p, L.cf_slots.p, u, L.ghostCur());
+		hipLaunchKernelGGL(k_cf_ghost3d<N>, grid, blk, 0, g->stream, L.cf_desc.p, L.cf_slots.p, src.u, L.ghostCur());
 }
 
-template <int N> int prepareGhosts(te_gmg *g, LevelHost &L, const double *u, const ProlongSrc *ps = nullptr)
+template <int N> int prepareGhosts(te_gmg *g, LevelHost &L, const GhostSrc &src, bool patch_op = false)
 {
-	if (L.patch_local) return TE_OK; // the patch operator reads no neighbour
+	if (patch_op) return TE_OK; // the patch operator (LevelHost::dev) reads no neighbour
 	L.ghost_has_v = false;
 	if (L.nremote > 0) {
 		// the face layers of an iterate that exists only as such already sit in send order (LevelHost::f6off): sent from there
-		const bool direct = L.pack_f6 && !ps && L.f6Off();
-		const bool pushed = !direct && packFaces<N>(g, L, u, ps, true);
-		int        rc     = pushed ? pushFinish(g, L, 1, g->stream) : faceExchange(g, L, direct ? L.pack_f6 : L.sendbuf.p);
+		const bool direct = src.f6 && !src.ps && L.f6Off();
+		const bool pushed = !direct && packFaces<N>(g, L, src, true);
+		int        rc     = pushed ? pushFinish(g, L, 1, g->stream) : faceExchange(g, L, direct ? src.f6 : L.sendbuf.p);
 		if (rc) return rc;
 	}
 	if (L.ncf == 0) return TE_OK;
-	cfGhosts<N>(g, L, u, ps);
+	cfGhosts<N>(g, L, src);
 	return TE_OK;
 }
 
@@ -77,8 +82,8 @@ template <int N> int prepareGhosts(te_gmg *g, LevelHost &L, const double *u, con
 // exchange goes to the communication stream and the interior patches (no ghost-slot face) are computed
 // underneath it; the boundary patches follow once the receive has landed. (north star: "ghost-cell
 // exchange ... overlapped with interior smoothing")
-template <int N, class F> int withGhosts(te_gmg *g, LevelHost &L, const double *u, F launch_, const double *xf_in = nullptr,
-                                         double *xf_out = nullptr, const ProlongSrc *ps = nullptr)
+template <int N, class F> int withGhosts(te_gmg *g, LevelHost &L, const GhostSrc &src, F launch_, const double *xf_in = nullptr,
+                                         double *xf_out = nullptr, bool patch_op = false)
 {
 	auto launch = [&](LevelDev D) {
 		D.xf     = xf_in;
@@ -94,10 +99,10 @@ template <int N, class F> int withGhosts(te_gmg *g, LevelHost &L, const double *
 	// ranks) the cycle is 525 us with the split and 475 us without it.
 	L.ghost_has_v = false;
 	const int mode = L.overlap_mode >= 0 ? L.overlap_mode : (L.P < g->cfg.num(O_OVERLAP_MIN, 768) ? 0 : (g->cfg.num(O_OVERLAP_MODE, 1) == 2 ? 2 : 1));
-	if (L.patch_local || g->recording || L.nremote == 0 || !g->overlap || L.n_int == 0 || mode == 0) {
-		int rc = prepareGhosts<N>(g, L, u, ps);
+	if (patch_op || g->recording || L.nremote == 0 || !g->overlap || L.n_int == 0 || mode == 0) {
+		int rc = prepareGhosts<N>(g, L, src, patch_op);
 		if (rc) return rc;
-		launch(L.dev());
+		launch(L.dev(patch_op));
 		return TE_OK;
 	}
 	if (mode == 2) {
@@ -110,15 +115,15 @@ template <int N, class F> int withGhosts(te_gmg *g, LevelHost &L, const double *
 		hipError_t e = hipEventRecord(g->ev_recv, g->stream);
 		std::swap(g->stream, g->comm_stream);
 		HIPCHK(e);
-		const bool pushed = packFaces<N>(g, L, u, ps, true);
+		const bool pushed = packFaces<N>(g, L, src, true);
 		int        rc     = pushed ? pushFinish(g, L, 1, g->stream) : faceExchange(g, L, L.sendbuf.p);
 		if (rc) return rc;
-		if (L.ncf > 0) cfGhosts<N>(g, L, u, ps);
+		if (L.ncf > 0) cfGhosts<N>(g, L, src);
 		launch(L.devPart(true));
 		HIPCHK(hipStreamWaitEvent(g->stream, g->ev_recv, 0));
 		return TE_OK;
 	}
-	packFaces<N>(g, L, u, ps);
+	packFaces<N>(g, L, src);
 	HIPCHK(hipEventRecord(g->ev_pack, g->stream));
 	HIPCHK(hipStreamWaitEvent(g->comm_stream, g->ev_pack, 0));
 	int rc = faceExchange(g, L, L.sendbuf.p, g->comm_stream);
@@ -126,7 +131,7 @@ template <int N, class F> int withGhosts(te_gmg *g, LevelHost &L, const double *
 	HIPCHK(hipEventRecord(g->ev_recv, g->comm_stream));
 	launch(L.devPart(false)); // interior, concurrent with the exchange
 	HIPCHK(hipStreamWaitEvent(g->stream, g->ev_recv, 0));
-	if (L.ncf > 0) cfGhosts<N>(g, L, u, ps);
+	if (L.ncf > 0) cfGhosts<N>(g, L, src);
 	launch(L.devPart(true)); // boundary
 	return TE_OK;
 }

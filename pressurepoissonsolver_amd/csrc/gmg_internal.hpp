@@ -198,9 +198,8 @@ struct LevelHost {
 	// stencil tables
 	DevBuf<int32_t> face_kind, face_src;
 	// the same with every neighbour face closed as homogeneous Dirichlet: the PATCH operator, StarPatchOp::apply
-	// (StarPatchOp.h:204-319); patch_local selects it for one launch (te_patch_apply)
+	// (StarPatchOp.h:204-319); dev(patch_op = true) selects it for one launch (te_patch_apply)
 	DevBuf<int32_t> face_kind_patch;
-	bool            patch_local = false;
 	DevBuf<double>  face_kadj, rh2, ghost;
 	int             nslots = 0;
 	// coarse/fine faces
@@ -256,23 +255,23 @@ struct LevelHost {
 	std::vector<int32_t> brestrict_host;
 	DevBuf<int32_t>      brestrict;
 
-	Level2D dev2() const
+	Level2D dev2(bool patch_op = false) const
 	{
 		Level2D L;
 		L.P         = P;
 		L.n         = n;
-		L.face_kind = patch_local ? face_kind_patch.p : face_kind.p;
+		L.face_kind = patch_op ? face_kind_patch.p : face_kind.p;
 		L.face_src  = face_src.p;
 		L.face_kadj = face_kadj.p;
 		L.rh2       = rh2.p;
 		L.ghost     = ghostCur();
 		return L;
 	}
-	LevelDev dev() const
+	LevelDev dev(bool patch_op = false) const
 	{
 		LevelDev L;
 		L.P         = P;
-		L.face_kind = patch_local ? face_kind_patch.p : face_kind.p;
+		L.face_kind = patch_op ? face_kind_patch.p : face_kind.p;
 		L.face_src  = face_src.p;
 		L.face_kadj = face_kadj.p;
 		L.rh2       = rh2.p;
@@ -351,10 +350,9 @@ struct LevelHost {
 	int                gdesc_key = -1;
 	const double      *fcorr_zeroed_for = nullptr; // the coarse level's side array this level's gather has zeroed once (its all-zero planes are never written)
 	DevBuf<double> e4buf; // 2D: [P][4][n] edge layers of an iterate that is never stored (the 2D twin of f6buf)
-	const double  *pack_f6 = nullptr; // set while that iterate is the one whose faces travel to other ranks
-	// reference smoother, opts.fuse = 3: the zero-guess pre-sweep is asked to store only the face layers of its result (ps_faces_req,
-	// set by the cycle); ps_faces: it did -- f6buf holds them, the level's u is undefined until the post-sweep rewrites it
-	bool ps_faces_req = false, ps_faces = false;
+	// reference smoother, opts.fuse = 3: the zero-guess pre-sweep stored only the face layers of its result (PatchSolveOpts::faces_only):
+	// f6buf holds them, the level's u is undefined until the post-sweep rewrites it
+	bool ps_faces = false;
 	DevBuf<double> xfbuf[2];
 	int            xf_cur       = 0;
 	const double  *xf_valid_for = nullptr;
@@ -402,7 +400,6 @@ struct te_gmg {
 	hipEvent_t  ev_pack = nullptr, ev_recv = nullptr;
 	bool        overlap = true;
 	bool        in_cycle = false; // te_vcycle in progress: the levels' xf_valid_for bookkeeping is trustworthy
-	bool        no_xf_export = false; // the patch solve in progress is the last kernel on its level: nobody reads its x faces
 	// te_bicgstab: the cycle's result is the very next operand of an operator application -- level 0's last sweep exports its
 	// compact x-face columns after all, and they stay valid when the cycle returns (the stencil kernel then reads 256 contiguous
 	// bytes per plane and side instead of 8 of every 128-byte line of the neighbour patch: 1.24 x -> 1.0x of its algorithmic bytes)
@@ -698,10 +695,10 @@ struct WatchdogBatch {
 // ---- gmg_launch3d.hip (the dispatchers hand 2D levels to gmg_launch2d.hip)
 template <int MODE> int launchStencil(te_gmg *g, LevelHost &L, const double *u, const double *f, double *out, double omega,
                                       RestrictDst rd = RestrictDst(), const double *xf_in = nullptr, int redmode = RED_NONE,
-                                      const double *red_a = nullptr, int *red_items = nullptr);
-extern template int launchStencil<MODE_APPLY>(te_gmg *, LevelHost &, const double *, const double *, double *, double, RestrictDst, const double *, int, const double *, int *);
-extern template int launchStencil<MODE_RESID>(te_gmg *, LevelHost &, const double *, const double *, double *, double, RestrictDst, const double *, int, const double *, int *);
-extern template int launchStencil<MODE_JACOBI>(te_gmg *, LevelHost &, const double *, const double *, double *, double, RestrictDst, const double *, int, const double *, int *);
+                                      const double *red_a = nullptr, int *red_items = nullptr, bool patch_op = false);
+extern template int launchStencil<MODE_APPLY>(te_gmg *, LevelHost &, const double *, const double *, double *, double, RestrictDst, const double *, int, const double *, int *, bool);
+extern template int launchStencil<MODE_RESID>(te_gmg *, LevelHost &, const double *, const double *, double *, double, RestrictDst, const double *, int, const double *, int *, bool);
+extern template int launchStencil<MODE_JACOBI>(te_gmg *, LevelHost &, const double *, const double *, double *, double, RestrictDst, const double *, int, const double *, int *, bool);
 int resweepProlong(te_gmg *g, LevelHost &L, const double *f, double *out, const double *prolong_from, double *xf_out, const double *fcorr_in);
 int interfaceResidRestrict(te_gmg *g, LevelHost &L, const double *u, const double *xf, double *coarse, size_t coarse_n);
 int zeroSweepResid(te_gmg *g, LevelHost &L, const double *f, double *out, double *coarse, double *xf_out, bool store_u,
@@ -713,8 +710,13 @@ int residRestrict(te_gmg *g, LevelHost &L, const double *u, const double *f, dou
 bool psOnePass(const te_gmg *g, const LevelHost &L);  // (gmg_patchsolve.hip) the single-pass patch-solve kernels on this level
 int  psSymCount(const te_gmg *g, const LevelHost &L); // ... of them, patches that take k_ps_sym
 bool psAllSym32(const te_gmg *g, const LevelHost &L); // 32^3 patches, every one through the single-pass k_ps_sym
-int patchSolve(te_gmg *g, LevelHost &L, const double *f, double *u, bool zero_guess = false, const double *prolong_from = nullptr,
-               bool *swapped = nullptr);
+struct PatchSolveOpts { // one sweep of the reference smoother
+	bool          zero_guess   = false;
+	const double *prolong_from = nullptr;
+	bool          faces_only   = false; // a zero-guess solve stores only the six face layers of its result where the level's kernel can (L.ps_faces: it did)
+	bool          export_xf    = true;  // false: the solve is the last kernel on its level inside te_vcycle, nobody reads its x-face columns
+};
+int patchSolve(te_gmg *g, LevelHost &L, const double *f, double *u, const PatchSolveOpts &o = PatchSolveOpts(), bool *swapped = nullptr);
 int doRestrict(te_gmg *g, int fine_level, const double *fine, double *coarse);
 int doProlong(te_gmg *g, int fine_level, const double *coarse, double *fine);
 // ---- gmg_prolong.hip
@@ -728,12 +730,12 @@ void fmgFree(te_gmg *g); // (te_gmg_release_workspace, te_gmg_destroy)
 void regridFree(te_gmg *g); // (te_gmg_destroy)
 int  regridMapUpload(te_gmg *src, te_gmg *dst, const char *who, const int32_t **map_dev); // one row per patch of dst, in dst's buffer
 // ---- gmg_launch2d.hip
-int prepareGhosts2d(te_gmg *g, LevelHost &L, const double *u);
+int prepareGhosts2d(te_gmg *g, LevelHost &L, const double *u, bool patch_op = false);
 template <int MODE> int launchStencil2d(te_gmg *g, LevelHost &L, const double *u, const double *f, double *out, double omega, int redmode = RED_NONE,
-                                        const double *red_a = nullptr, int *red_items = nullptr);
-extern template int launchStencil2d<MODE_APPLY>(te_gmg *, LevelHost &, const double *, const double *, double *, double, int, const double *, int *);
-extern template int launchStencil2d<MODE_RESID>(te_gmg *, LevelHost &, const double *, const double *, double *, double, int, const double *, int *);
-extern template int launchStencil2d<MODE_JACOBI>(te_gmg *, LevelHost &, const double *, const double *, double *, double, int, const double *, int *);
+                                        const double *red_a = nullptr, int *red_items = nullptr, bool patch_op = false);
+extern template int launchStencil2d<MODE_APPLY>(te_gmg *, LevelHost &, const double *, const double *, double *, double, int, const double *, int *, bool);
+extern template int launchStencil2d<MODE_RESID>(te_gmg *, LevelHost &, const double *, const double *, double *, double, int, const double *, int *, bool);
+extern template int launchStencil2d<MODE_JACOBI>(te_gmg *, LevelHost &, const double *, const double *, double *, double, int, const double *, int *, bool);
 int residualSumsq2d(te_gmg *g, LevelHost &L, const double *u, const double *f, double *out, int *blocks);
 int launchRbgs2d(te_gmg *g, LevelHost &L, const double *u, const double *f, double *out, bool zero_guess = false, const double *prolong_from = nullptr);
 int residRestrict2d(te_gmg *g, LevelHost &L, const double *u, const double *f, double *coarse);

@@ -4,9 +4,9 @@
 namespace tei
 {
 // ------------------------------------------------------------------------------ 2D launches
-int prepareGhosts2d(te_gmg *g, LevelHost &L, const double *u)
+int prepareGhosts2d(te_gmg *g, LevelHost &L, const double *u, bool patch_op)
 {
-	if (L.patch_local) return TE_OK;
+	if (patch_op) return TE_OK; // the patch operator reads no neighbour
 	if (L.nremote > 0) {
 		{
 			Timed t(g, KC_PACK, (size_t) L.nremote * L.nf);
@@ -25,10 +25,10 @@ int prepareGhosts2d(te_gmg *g, LevelHost &L, const double *u)
 // operand of the dot product); *red_items = their number (the caller runs k_reduce_final2 over them) -- the 2D twin of
 // k_stencil3d's RED: te_bicgstab's dot products and the residual norm without passes of their own
 template <int MODE> int launchStencil2d(te_gmg *g, LevelHost &L, const double *u, const double *f, double *out, double omega, int redmode,
-                                        const double *red_a, int *red_items)
+                                        const double *red_a, int *red_items, bool patch_op)
 {
 	if (red_items) *red_items = 0;
-	int rc = prepareGhosts2d(g, L, u);
+	int rc = prepareGhosts2d(g, L, u, patch_op);
 	if (rc) return rc;
 	if (redmode != RED_NONE && L.P > 0) {
 		if constexpr (MODE == MODE_JACOBI) {
@@ -39,18 +39,18 @@ template <int MODE> int launchStencil2d(te_gmg *g, LevelHost &L, const double *u
 			const int blocks = gridFor((size_t) L.P * L.nc / 2, 256, (int) std::min<size_t>((size_t) 1 << 30, g->partial.n / 2));
 			Timed     t(g, MODE == MODE_APPLY ? KC_APPLY_DOT : KC_RESID, (size_t) L.P * L.nc);
 			if (redmode == RED_OUT_A)
-				hipLaunchKernelGGL((k_stencil2d<MODE, RED_OUT_A>), dim3(blocks), dim3(256), 0, g->stream, L.dev2(), u, f, out, omega, g->partial.p, red_a);
+				hipLaunchKernelGGL((k_stencil2d<MODE, RED_OUT_A>), dim3(blocks), dim3(256), 0, g->stream, L.dev2(patch_op), u, f, out, omega, g->partial.p, red_a);
 			else if (redmode == RED_OUT_A_OUT)
-				hipLaunchKernelGGL((k_stencil2d<MODE, RED_OUT_A_OUT>), dim3(blocks), dim3(256), 0, g->stream, L.dev2(), u, f, out, omega, g->partial.p, red_a);
+				hipLaunchKernelGGL((k_stencil2d<MODE, RED_OUT_A_OUT>), dim3(blocks), dim3(256), 0, g->stream, L.dev2(patch_op), u, f, out, omega, g->partial.p, red_a);
 			else
-				hipLaunchKernelGGL((k_stencil2d<MODE, RED_OUT_OUT>), dim3(blocks), dim3(256), 0, g->stream, L.dev2(), u, f, out, omega, g->partial.p, red_a);
+				hipLaunchKernelGGL((k_stencil2d<MODE, RED_OUT_OUT>), dim3(blocks), dim3(256), 0, g->stream, L.dev2(patch_op), u, f, out, omega, g->partial.p, red_a);
 			if (red_items) *red_items = blocks;
 			HIPCHK(hipGetLastError());
 			return TE_OK;
 		}
 	}
 	Timed t(g, MODE == MODE_APPLY ? KC_APPLY : (MODE == MODE_RESID ? KC_RESID : KC_JACOBI), (size_t) L.P * L.nc);
-	hipLaunchKernelGGL(k_stencil2d<MODE>, dim3(gridFor((size_t) L.P * L.nc / 2, 256, 65536)), dim3(256), 0, g->stream, L.dev2(),
+	hipLaunchKernelGGL(k_stencil2d<MODE>, dim3(gridFor((size_t) L.P * L.nc / 2, 256, 65536)), dim3(256), 0, g->stream, L.dev2(patch_op),
 	                   u, f, out, omega);
 	HIPCHK(hipGetLastError());
 	return TE_OK;
@@ -71,7 +71,7 @@ static int tpb2d(const te_gmg *g) { return g->cfg.num(O_2D_TPB, 512) == 256 ? 25
 // their values into this rank's ghost slots
 int packProlongFaces2d(te_gmg *g, LevelHost &L, const double *u, const double *e4, const Prolong2D &ps)
 {
-	if (L.nremote == 0 || L.patch_local) return TE_OK;
+	if (L.nremote == 0) return TE_OK;
 	{
 		Timed t(g, KC_PACK, (size_t) L.nremote * L.nf);
 		hipLaunchKernelGGL(k_pack_faces_prolong2d, dim3(L.nremote), dim3(64), 0, g->stream, L.n, L.send_faces.p, u, e4, ps, L.sendbuf.p);
@@ -469,8 +469,8 @@ int resweepProlong2d(te_gmg *g, LevelHost &L, const double *f, double *out, cons
 	return TE_OK;
 }
 
-template int launchStencil2d<MODE_APPLY>(te_gmg *, LevelHost &, const double *, const double *, double *, double, int, const double *, int *);
-template int launchStencil2d<MODE_RESID>(te_gmg *, LevelHost &, const double *, const double *, double *, double, int, const double *, int *);
-template int launchStencil2d<MODE_JACOBI>(te_gmg *, LevelHost &, const double *, const double *, double *, double, int, const double *, int *);
+template int launchStencil2d<MODE_APPLY>(te_gmg *, LevelHost &, const double *, const double *, double *, double, int, const double *, int *, bool);
+template int launchStencil2d<MODE_RESID>(te_gmg *, LevelHost &, const double *, const double *, double *, double, int, const double *, int *, bool);
+template int launchStencil2d<MODE_JACOBI>(te_gmg *, LevelHost &, const double *, const double *, double *, double, int, const double *, int *, bool);
 } // namespace tei
 

@@ -31,9 +31,9 @@ void launchStencilZS(te_gmg *g, dim3 grid, const LevelDev &D_, const double *u, 
 
 // redmode != RED_NONE: the kernel leaves one pair of partial sums per work item in g->partial (red_a: the second operand
 // of the dot product); *red_items = their number (the caller runs k_reduce_final2 over them)
-template <int N, int MODE> int launchStencilN(te_gmg *g, LevelHost &L, const double *u, const double *f, double *out,
-                                              double omega, RestrictDst rd = RestrictDst(), const double *xf_in = nullptr,
-                                              int redmode = RED_NONE, const double *red_a = nullptr, int *red_items = nullptr)
+template <int N, int MODE> int launchStencilN(te_gmg *g, LevelHost &L, const double *u, const double *f, double *out, double omega,
+                                              RestrictDst rd = RestrictDst(), const double *xf_in = nullptr, int redmode = RED_NONE,
+                                              const double *red_a = nullptr, int *red_items = nullptr, bool patch_op = false)
 {
 	const int zs = stencilSlabs<N>(g, L.P);
 	if (redmode != RED_NONE) {
@@ -51,14 +51,14 @@ template <int N, int MODE> int launchStencilN(te_gmg *g, LevelHost &L, const dou
 			launchStencilZS<N, MODE, decltype(z)::value>(g, slabGrid(D.count, zs), D, u, f, out, omega, rd, redmode, rs);
 		});
 	};
-	int rc = withGhosts<N>(g, L, u, launch, xf_in);
+	int rc = withGhosts<N>(g, L, {u}, launch, xf_in, nullptr, patch_op);
 	if (rc) return rc;
 	HIPCHK(hipGetLastError());
 	return TE_OK;
 }
 
 template <int MODE> int launchStencil(te_gmg *g, LevelHost &L, const double *u, const double *f, double *out, double omega,
-                                      RestrictDst rd, const double *xf_in, int redmode, const double *red_a, int *red_items)
+                                      RestrictDst rd, const double *xf_in, int redmode, const double *red_a, int *red_items, bool patch_op)
 {
 	if (red_items) *red_items = 0;
 	if (L.P == 0) return TE_OK;
@@ -66,10 +66,10 @@ template <int MODE> int launchStencil(te_gmg *g, LevelHost &L, const double *u, 
 		if constexpr (MODE == MODE_RESID_RESTRICT)
 			return te::fail(TE_EUNSUPPORTED, "fused residual+restrict has no 2D kernel");
 		else
-			return launchStencil2d<MODE>(g, L, u, f, out, omega, redmode, red_a, red_items);
+			return launchStencil2d<MODE>(g, L, u, f, out, omega, redmode, red_a, red_items, patch_op);
 	}
 	return dispatchN(L.n, [&](auto n) {
-		return launchStencilN<decltype(n)::value, MODE>(g, L, u, f, out, omega, rd, xf_in, redmode, red_a, red_items);
+		return launchStencilN<decltype(n)::value, MODE>(g, L, u, f, out, omega, rd, xf_in, redmode, red_a, red_items, patch_op);
 	});
 }
 
@@ -103,7 +103,7 @@ template <int N> int launchRbgsN(te_gmg *g, LevelHost &L, const double *u, const
 			launchRbgsKernel<N, false, true>(g, D, u, f, out, ps);
 		};
 		// neighbours on other ranks receive this rank's face layers of u + P(coarse) (exchange under the interior)
-		int rc = withGhosts<N>(g, L, u, launch, xf_in, xf_out, &ps);
+		int rc = withGhosts<N>(g, L, {u, nullptr, &ps}, launch, xf_in, xf_out);
 		if (rc) return rc;
 		HIPCHK(hipGetLastError());
 		return TE_OK;
@@ -121,7 +121,7 @@ template <int N> int launchRbgsN(te_gmg *g, LevelHost &L, const double *u, const
 		Timed t(g, rbgsSlabs<N>(g, D.count) > 1 ? KC_RBGS_SLABS : KC_RBGS, (size_t) D.count * L.nc);
 		launchRbgsKernel<N, false, false>(g, D, u, f, out, ProlongSrc());
 	};
-	int rc = withGhosts<N>(g, L, u, launch, xf_in, xf_out);
+	int rc = withGhosts<N>(g, L, {u}, launch, xf_in, xf_out);
 	if (rc) return rc;
 	HIPCHK(hipGetLastError());
 	return TE_OK;
@@ -201,8 +201,8 @@ int doProlong(te_gmg *g, int fine_level, const double *coarse, double *fine)
 	return dispatchN(L.n, [&](auto n) { return prolongN<decltype(n)::value>(g, L, coarse, fine); });
 }
 
-template int launchStencil<MODE_APPLY>(te_gmg *, LevelHost &, const double *, const double *, double *, double, RestrictDst, const double *, int, const double *, int *);
-template int launchStencil<MODE_RESID>(te_gmg *, LevelHost &, const double *, const double *, double *, double, RestrictDst, const double *, int, const double *, int *);
-template int launchStencil<MODE_JACOBI>(te_gmg *, LevelHost &, const double *, const double *, double *, double, RestrictDst, const double *, int, const double *, int *);
+template int launchStencil<MODE_APPLY>(te_gmg *, LevelHost &, const double *, const double *, double *, double, RestrictDst, const double *, int, const double *, int *, bool);
+template int launchStencil<MODE_RESID>(te_gmg *, LevelHost &, const double *, const double *, double *, double, RestrictDst, const double *, int, const double *, int *, bool);
+template int launchStencil<MODE_JACOBI>(te_gmg *, LevelHost &, const double *, const double *, double *, double, RestrictDst, const double *, int, const double *, int *, bool);
 } // namespace tei
 

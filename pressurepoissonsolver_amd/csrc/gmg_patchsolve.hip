@@ -22,13 +22,12 @@ bool psAllSym32(const te_gmg *g, const LevelHost &L)
 	return L.dim == 3 && L.n == 32 && L.P > 0 && !g->cfg.has(O_PS_SLOW) && psOnePass(g, L) && psSymCount(g, L) == L.P;
 }
 
-template <int N> int patchSolveN(te_gmg *g, LevelHost &L, const double *f, double *u, double *s0, double *s1,
-                                 bool zero_guess, const double *prolong_from)
+template <int N> int patchSolveN(te_gmg *g, LevelHost &L, const double *f, double *u, double *s0, double *s1, const PatchSolveOpts &o)
 {
-	const size_t total = (size_t) L.P * L.nc;
-	int          rc;
-	const bool   faces_req = L.ps_faces_req && zero_guess; // (a request holds for the very next sweep only)
-	L.ps_faces_req         = false;
+	const size_t  total        = (size_t) L.P * L.nc;
+	const bool    zero_guess   = o.zero_guess, faces_req = o.faces_only && zero_guess;
+	const double *prolong_from = o.prolong_from;
+	int           rc;
 	if (!g->cfg.has(O_PS_SLOW)) { // (3D patches are 4, 8, 16 or 32 cells wide)
 		// matrix-core path (patchsolve32.hpp; 16^3 patches: patchsolve16.hpp): interface terms on the face layers only, then x,y forward
 		// per plane; z forward + eigenvalue divide + z inverse; x,y inverse. A zero initial guess has no
@@ -47,10 +46,7 @@ template <int N> int patchSolveN(te_gmg *g, LevelHost &L, const double *f, doubl
 		L.xf_valid_for      = nullptr; // u is rewritten in place
 		if (!zero_guess) {
 			const ProlongSrc ps = prolongSrc(L, prolong_from);
-			L.pack_f6           = L.ps_faces ? L.f6buf.p : nullptr;
-			rc        = prepareGhosts<N>(g, L, u, prolong_from ? &ps : nullptr);
-			L.pack_f6 = nullptr;
-			if (rc) return rc;
+			if ((rc = prepareGhosts<N>(g, L, {u, L.ps_faces ? L.f6buf.p : nullptr, prolong_from ? &ps : nullptr}))) return rc;
 			Timed    t(g, KC_PATCH_RHS, (size_t) L.P * 6 * L.nf);
 			LevelDev D = L.dev();
 			D.xf       = L.ps_faces ? nullptr : xf_in;
@@ -114,7 +110,7 @@ template <int N> int patchSolveN(te_gmg *g, LevelHost &L, const double *f, doubl
 			const int32_t *lst_mix = (n_sym > 0 && n_mix > 0) ? L.ps_list.p + n_sym : nullptr;
 			if (n_sym > 0) {
 				const dim3 gs(std::min(n_sym, ncu));
-				double    *xo = (g->in_cycle && n_mix == 0 && !g->no_xf_export) ? L.xfbuf[L.xf_cur ^ 1].p : nullptr; // (k_ps_fused does not export)
+				double    *xo = (g->in_cycle && n_mix == 0 && o.export_xf) ? L.xfbuf[L.xf_cur ^ 1].p : nullptr; // (k_ps_fused does not export)
 				const bool faces = faces_req && n_mix == 0 && L.f6buf.p;
 				if (faces) { // only the face layers of the result: see k_ps_sym<CORR, FACES>
 					L.f6_tab = false; // (written as [p][6])
@@ -188,7 +184,7 @@ template <int N> int patchSolveN(te_gmg *g, LevelHost &L, const double *f, doubl
 		Timed t(g, KC_VECOP, total);
 		HIPCHK(hipMemsetAsync(u, 0, sizeof(double) * total, g->stream));
 	}
-	if ((rc = prepareGhosts<N>(g, L, u))) return rc;
+	if ((rc = prepareGhosts<N>(g, L, {u}))) return rc;
 	{
 		Timed t(g, KC_PATCH_RHS, total);
 		hipLaunchKernelGGL(k_patch_rhs3d<N>, dim3(gridFor(total, 256)), dim3(256), 0, g->stream, L.dev(), u, f, s0);
@@ -212,7 +208,7 @@ template <int N> int patchSolveN(te_gmg *g, LevelHost &L, const double *f, doubl
 	return TE_OK;
 }
 
-int patchSolve(te_gmg *g, LevelHost &L, const double *f, double *u, bool zero_guess, const double *prolong_from, bool *swapped)
+int patchSolve(te_gmg *g, LevelHost &L, const double *f, double *u, const PatchSolveOpts &o, bool *swapped)
 {
 	bool dummy;
 	if (!swapped) swapped = &dummy;
@@ -220,10 +216,10 @@ int patchSolve(te_gmg *g, LevelHost &L, const double *f, double *u, bool zero_gu
 	if (L.P == 0) return TE_OK; // (no patches: no faces towards other ranks either)
 	double *s0 = L.r->d, *s1 = L.t->d;
 	if (L.dim == 2) {
-		int rc = patchSolve2d(g, L, f, u, s0, s1, zero_guess, swapped, prolong_from);
+		int rc = patchSolve2d(g, L, f, u, s0, s1, o.zero_guess, swapped, o.prolong_from);
 		if (rc == TE_OK && *swapped && swapped == &dummy) return te::fail(TE_ESTATE, "patchSolve: 2D result left in scratch");
 		return rc;
 	}
-	return dispatchN(L.n, [&](auto n) { return patchSolveN<decltype(n)::value>(g, L, f, u, s0, s1, zero_guess, prolong_from); });
+	return dispatchN(L.n, [&](auto n) { return patchSolveN<decltype(n)::value>(g, L, f, u, s0, s1, o); });
 }
 } // namespace tei

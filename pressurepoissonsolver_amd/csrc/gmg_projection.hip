@@ -39,7 +39,7 @@ template <int N, bool PROJECT> static int gradientN(te_gmg *g, LevelHost &L, con
 			                   alpha);
 		});
 	};
-	int rc = withGhosts<N>(g, L, u, launch);
+	int rc = withGhosts<N>(g, L, {u}, launch);
 	if (rc) return rc;
 	HIPCHK(hipGetLastError());
 	return TE_OK;

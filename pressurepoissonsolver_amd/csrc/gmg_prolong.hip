@@ -22,7 +22,7 @@ template <int N> static int prolongLinearN(te_gmg *g, LevelHost &L, LevelHost &C
 		});
 	};
 	// (one rank: the coarse level has no remote face, so withGhosts launches once, over the whole level's tables)
-	int rc = withGhosts<N>(g, C, coarse, launch);
+	int rc = withGhosts<N>(g, C, {coarse}, launch);
 	if (rc) return rc;
 	HIPCHK(hipGetLastError());
 	return TE_OK;
@@ -57,7 +57,7 @@ template <int N> static int prolongQuadraticN(te_gmg *g, LevelHost &L, LevelHost
 			                   L.orth.p, coarse, fine);
 		});
 	};
-	int rc = withGhosts<N>(g, C, coarse, launch);
+	int rc = withGhosts<N>(g, C, {coarse}, launch);
 	if (rc) return rc;
 	HIPCHK(hipGetLastError());
 	return TE_OK;

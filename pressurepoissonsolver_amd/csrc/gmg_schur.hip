@@ -142,7 +142,7 @@ static int solveWith(te_gmg *g, LevelHost &L, SchurLevel &S, const double *f, co
 		f = S.w->d;
 	}
 	bool swapped = false;
-	if ((rc = patchSolve(g, L, f, u, true, nullptr, &swapped))) return rc;
+	if ((rc = patchSolve(g, L, f, u, {true}, &swapped))) return rc;
 	if (swapped) *res = L.t->d; // (2D: the solve's result stays in its scratch)
 	return TE_OK;
 }
@@ -318,9 +318,7 @@ int te_apply_with_interface(te_gmg *g, int level, const te_vec *u, const te_vec 
 			return rc;
 		if (u == f) return te::fail(TE_EINVAL, "te_apply_with_interface: in-place apply is not supported");
 		// the patch operator (neighbour faces closed as homogeneous Dirichlet), then + 2 gamma / h^2 on the face layers
-		L->patch_local = true;
-		rc             = launchStencil<MODE_APPLY>(g, *L, u->d, nullptr, f->d, 0.0);
-		L->patch_local = false;
+		rc = launchStencil<MODE_APPLY>(g, *L, u->d, nullptr, f->d, 0.0, RestrictDst(), nullptr, RED_NONE, nullptr, nullptr, true);
 		if (rc || (rc = ifaceCorr(g, *L, *S, gamma->d))) return rc;
 		return ifaceRhs(g, *L, *S, f->d, f->d, true);
 	});

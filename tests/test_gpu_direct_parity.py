@@ -355,3 +355,26 @@ def test_hip_against_live_reference_code(name, n, div, dim):
     g.smooth(dff, du, smoother=capi.SMOOTH_PATCH_SOLVE)
     rhs = refslice.add_iface_rhs(L, refslice.interp(L, u), f)
     assert np.abs(refslice.patch_apply(L, du.download()) - rhs).max() <= 1e-11 * np.abs(rhs).max()
+
+
+@pytest.mark.parametrize("name,n,div,dim", [("uniform", 8, 1, 3), ("2d2ref.bin", 16, 1, 2)])
+def test_patch_operator_leaves_no_trace_on_its_level(name, n, div, dim):
+    """te_patch_apply and te_apply_with_interface select the patch operator for their own launch only: te_apply on the same
+    level gives the same bits before and after them. (Every patch of these meshes has a neighbour face, the 2D one a
+    coarse/fine face as well, so the two operators differ.)"""
+    m, H, levels = util.setup(name, n, div, dim=dim)
+    g, L = capi.GMG(H), levels[0]
+    du = g.new_vector(0, util.rand_vec(L.size, 93))
+    d1, d2, d3 = g.new_vector(0), g.new_vector(0), g.new_vector(0)
+    g.apply(du, d1)
+    g.patch_apply(du, d2)
+    g.apply(du, d3)
+    a1 = d1.download()
+    assert np.array_equal(a1, d3.download())
+    assert not np.array_equal(a1, d2.download())
+    if dim == 3:
+        dgamma, d4, d5 = g.new_iface_vector(0), g.new_vector(0), g.new_vector(0)
+        g.iface_interp(du, dgamma)
+        g.apply_with_interface(du, dgamma, d4)
+        g.apply(du, d5)
+        assert np.array_equal(a1, d5.download())
