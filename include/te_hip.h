@@ -233,6 +233,9 @@ int te_vec_scale_then_add(te_vec *v, double alpha, const te_vec *b);
 int te_vec_scale_then_add_scaled(te_vec *v, double alpha, double beta, const te_vec *b);
 int te_vec_scale_then_add_scaled2(te_vec *v, double alpha, double beta, const te_vec *b,
                                   double gamma, const te_vec *c);
+/* v[i] *= b[i], for vectors of any one kind (domain, interface, boundary, face); TE_EINVAL when v and b differ in solver, level or
+ * kind. Nothing in Vector.h; what beta (.) grad p is for a face vector. */
+int te_vec_multiply(te_vec *v, const te_vec *b);
 /* local (this rank's) partial results; the caller all-reduces (Vector.h:294,306,319) */
 int te_vec_two_norm_sq(const te_vec *v, double *out);
 int te_vec_inf_norm(const te_vec *v, double *out);
@@ -574,6 +577,59 @@ int te_init_problem_sides(te_gmg *g, int level, int problem, te_vec *f, te_vec *
 int te_gradient(te_gmg *g, int level, const te_vec *u, const te_vec *bdata, te_vec *G);
 int te_divergence(te_gmg *g, int level, double alpha, const te_vec *U, te_vec *out);
 int te_project(te_gmg *g, int level, double alpha, const te_vec *p, const te_vec *bdata, te_vec *U);
+
+/* The variable-coefficient operator A_b u = div(beta grad u): the pressure equation of a flow with variable density,
+ * div((1 / rho) grad p) = div(u*) / dt. Nothing in the reference has it. A second, unfused path next to the Laplacian's, taken only
+ * while a coefficient is set; with none set every call gives the bits it gave before these entry points existed. Single rank.
+ *
+ * beta is a FACE vector of the level (te_vec_create_faces: per patch LO_a then HI_a). A face shared by two patches is stored by
+ * both: the caller keeps the two copies equal and every entry > 0; nothing checks this. rh2_a = 1 / h_a^2. u_lo / u_hi = the cell's
+ * neighbours along axis a; across a patch face exactly the ghost te_apply reads there: the neighbour's cell, 2 gamma - m on a
+ * coarse/fine face, -m on a physical Dirichlet face, +m on a Neumann face (m = the cell just inside). b_lo / b_hi = beta on the cell's
+ * lower / upper a-face: LO_a[c], and LO_a[c + e_a] or HI_a on the patch's upper face.
+ *   operator   (A_b u)[c] = sum over a = x, y, z in that order of (b_hi (u_hi - u_c) - b_lo (u_c - u_lo)) * rh2_a; up to rounding
+ *              te_divergence(1, beta (.) te_gradient(u, NULL)).
+ *   residual   r = f - A_b u.
+ *   RB-GS      patch-local, red = (x + y + z) even first; ghosts of faces with a neighbour frozen at the old iterate, coarse/fine
+ *              included. u_c <- (o - f_c) / d; o = sum over sides of b_s v_s rh2_a over interior neighbours and frozen ghosts
+ *              (physical faces contribute 0); d = sum over sides of b_s kappa_s rh2_a, kappa = 1 (interior or neighbour face),
+ *              2 (physical Dirichlet), 0 (physical Neumann). With beta = 1 the constant-coefficient sweep's numbers.
+ *   Jacobi     u <- u + omega (f - A_b u) / (-d_J), d_J = sum over sides of b_s (1 + adj_s) rh2_a; adj_s on a patch face: physical
+ *              Dirichlet +1, Neumann -1, this patch the fine side of a coarse/fine face -5/6 (3D) / -2/3 (2D), the coarse side +1/3;
+ *              anything else 0.
+ *   coarse levels   level l + 1's beta = the face average of level l's (te_faces_regrid's "coarsen" rule between the levels of one
+ *              hierarchy): coarse face (a, I, t) = the mean of the 2^(dim-1) fine faces that cover it, in the child with orthant bits
+ *              o_a = (I >= n/2), o_b = (t_b >= n/2) at fine plane 2 I - o_a n (the mid-plane is the upper child's plane 0);
+ *              3D ((p00 + p10) + (p01 + p11)) * 0.25, 2D (p0 + p1) * 0.5 (te_boundary_restrict's associations). A patch that copies
+ *              through hands its blocks on bit for bit. One writer per entry, no atomics.
+ *
+ * te_faces_restrict: coarse = that average of fine; face vectors of fine_level and fine_level + 1 (TE_EINVAL otherwise); TE_ESTATE
+ * (the message says "sharded") on a sharded hierarchy.
+ * te_gmg_set_coefficient: beta = a level-0 face vector of this solver (TE_EINVAL otherwise). The solver COPIES it (the caller may free
+ * or overwrite its vector) and restricts it level by level. The per-level copies are allocated at the first call and reused (a driver
+ * calls this every time step); te_gmg_destroy frees them. NULL clears the coefficient and keeps the buffers;
+ * te_gmg_release_workspace frees them too, but only while cleared. TE_ESTATE ("sharded") on a sharded hierarchy (NULL is accepted
+ * there: nothing to clear). A call that fails after its checks leaves NO coefficient set, never a partly updated one.
+ * te_gmg_has_coefficient: 0 or 1. te_gmg_coefficient: out = the level's beta (a face vector of that level); TE_ESTATE when none is set.
+ *
+ * While a coefficient is set:
+ *   te_apply, te_residual, te_residual_norm_sq use A_b (the norm is a second pass over r).
+ *   te_smooth takes TE_SMOOTH_RBGS and TE_SMOOTH_JACOBI; TE_SMOOTH_PATCH_SOLVE and TE_SMOOTH_PATCH_BCGS return TE_EUNSUPPORTED (their
+ *   patch solves invert the constant-coefficient patch operator).
+ *   te_vcycle runs a plain driver, GMG/Cycle.h:56-126 statement for statement: V and W, pre / mid / post / coarse sweeps, the solver's
+ *   interpolator (DIRECT or LINEAR), te_restrict's restriction. `fuse` is IGNORED (every value gives the same bits). `exact_coarse`
+ *   is IGNORED: the coarsest level runs coarse_sweeps sweeps of o->smoother -- a coarsest level of ONE patch wants coarse_sweeps of
+ *   the order of a few n (n = cells per axis) to be solved well enough. Other smoothers: TE_EUNSUPPORTED.
+ *   te_bicgstab applies A_b and preconditions with that cycle (its separate-pass form, what TE_NO_BICG_FUSE selects).
+ *   te_fmg, te_patch_apply and every call of the Schur route (te_iface_interp ... te_schur_solve) return TE_ESTATE; the message
+ *   contains "coefficient".
+ *   te_gradient, te_divergence, te_project, te_restrict, the prolongations, the BLAS-1 calls, the boundary and the regrid calls never
+ *   involve beta and are unchanged. te_add_boundary_rhs folds the CONSTANT-coefficient terms: with a coefficient the right-hand-side
+ *   terms of boundary data are -te_divergence(1, beta (.) te_gradient(0, bdata)). */
+int te_faces_restrict(te_gmg *g, int fine_level, const te_vec *fine, te_vec *coarse);
+int te_gmg_set_coefficient(te_gmg *g, const te_vec *beta);
+int te_gmg_has_coefficient(const te_gmg *g);
+int te_gmg_coefficient(te_gmg *g, int level, te_vec *out);
 
 /* kernel timing hooks for bench.py: HIP-event time of the last te_vcycle's dominant kernel */
 int te_gmg_profile(te_gmg *g, int enable);

@@ -114,6 +114,7 @@ SYMBOLS = {
     "te_vec_scale_then_add": (_I, [_P, _D, _P]),
     "te_vec_scale_then_add_scaled": (_I, [_P, _D, _D, _P]),
     "te_vec_scale_then_add_scaled2": (_I, [_P, _D, _D, _P, _D, _P]),
+    "te_vec_multiply": (_I, [_P, _P]),
     "te_vec_two_norm_sq": (_I, [_P, _PD]),
     "te_vec_inf_norm": (_I, [_P, _PD]),
     "te_vec_dot": (_I, [_P, _P, _PD]),
@@ -171,6 +172,10 @@ SYMBOLS = {
     "te_gradient": (_I, [_P, _I, _P, _P, _P]),
     "te_divergence": (_I, [_P, _I, _D, _P, _P]),
     "te_project": (_I, [_P, _I, _D, _P, _P, _P]),
+    "te_faces_restrict": (_I, [_P, _I, _P, _P]),
+    "te_gmg_set_coefficient": (_I, [_P, _P]),
+    "te_gmg_has_coefficient": (_I, [_P]),
+    "te_gmg_coefficient": (_I, [_P, _I, _P]),
     "te_integrate": (_I, [_P, _I, _P, _P]),
     "te_volume": (_I, [_P, _I, _P]),
 }
@@ -496,6 +501,7 @@ class Vec:
     def shift(self, delta): check(lib().te_vec_shift(self.h, delta))
     def copy(self, b): check(lib().te_vec_copy(self.h, b.h))
     def add(self, b): check(lib().te_vec_add(self.h, b.h))
+    def multiply(self, b): check(lib().te_vec_multiply(self.h, b.h))  # v[i] *= b[i] (any one kind of vector)
 
     def addScaled(self, alpha, a, beta=None, b=None):
         if b is None:
@@ -590,6 +596,22 @@ class GMG:
     def project(self, U, p, alpha=1.0, bdata=None, level=0):
         """U -= alpha grad p in one pass; collective"""
         check(lib().te_project(self.h, level, float(alpha), p.h, bdata.h if bdata is not None else None, U.h))
+
+    # ---- the variable-coefficient operator div(beta grad u) (te_hip.h: a second path, taken while a coefficient is set)
+    def set_coefficient(self, beta):
+        """beta: a level-0 face vector (copied, then restricted to every level); None clears the coefficient"""
+        check(lib().te_gmg_set_coefficient(self.h, beta.h if beta is not None else None))
+
+    def has_coefficient(self):
+        return bool(lib().te_gmg_has_coefficient(self.h))
+
+    def coefficient(self, level, out):
+        """out (a face vector of `level`) = the solver's beta on that level"""
+        check(lib().te_gmg_coefficient(self.h, level, out.h))
+
+    def faces_restrict(self, fine_level, fine, coarse):
+        """coarse (a face vector of fine_level + 1) = the face average of fine"""
+        check(lib().te_faces_restrict(self.h, fine_level, fine.h, coarse.h))
 
     def add_boundary_rhs(self, bdata, f, level=0):
         """f -= 2 g / h^2 on Dirichlet faces, f +- g_n / h on Neumann faces (Init.cpp:186-240, :89-146), in place"""

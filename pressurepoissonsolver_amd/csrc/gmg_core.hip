@@ -10,7 +10,8 @@ const char *kclassName[KC_COUNT] = {"stencil_apply", "stencil_resid", "stencil_j
                                     "restrict_fixup", "rbgs_resweep_prolong", "rbgs_zero_resid_restrict_faces",
                                     "rbgs_resweep_prolong_fcorr", "rbgs_zero_resid_restrict_faces_fcorr", "fcorr_gather", "patch_solve_mfma_faces",
                                     "bicg_update", "bicg_s", "bicg_p", "stencil_apply_dot", "patch_bcgs", "gradient", "divergence", "project", "prolong_linear", "prolong_quadratic", "boundary_restrict",
-                                    "indicator", "regrid", "regrid_faces"};
+                                    "indicator", "regrid", "regrid_faces",
+                                    "apply_coef", "resid_coef", "jacobi_coef", "rbgs_coef", "faces_restrict"};
 const char *optName[O_COUNT] = {"TE_2D_SIMPLE", "TE_2D_NO_MFMA", "TE_2D_NO_PF", "TE_2D_NO_MR_FUSE", "TE_2D_TPB", "TE_NO_FUSE2", "TE_NO_FUSE3",
                                 "TE_NO_FUSE3_CF", "TE_NO_CFP", "TE_NO_XF", "TE_NO_FCORR", "TE_NO_FCORR_CF", "TE_NO_GTAB", "TE_NO_OVERLAP",
                                 "TE_OVERLAP_MIN", "TE_NO_PS_FACES", "TE_PS_MODE", "TE_PS_SLOW", "TE_RBGS_NOSLAB", "TE_ZS_FORCE", "TE_NO_ZS8",
@@ -250,6 +251,7 @@ void te_gmg_destroy(te_gmg *g)
 	fmgFree(g);
 	schurFree(g);
 	regridFree(g);
+	coefFree(g);
 	for (auto &e : g->ev_pool) {
 		(void) hipEventDestroy(e.a);
 		(void) hipEventDestroy(e.b);
@@ -568,6 +570,7 @@ int te_gmg_release_workspace(te_gmg *g)
 				v = nullptr;
 			}
 			fmgFree(g);
+			if (!g->coef_on) coefFree(g); // (a coefficient that is set stays: the solver's operator depends on it)
 			return TE_OK;
 	});
 }

@@ -5,6 +5,7 @@ namespace tei
 {
 int smoothOnce(te_gmg *g, int level, const te_vec *f, te_vec *u, int smoother, double omega, bool zero_guess = false, bool faces_only = false)
 {
+	if (g->coef_on) return coefSmoothOnce(g, level, f, u, smoother, omega); // (te_smooth; the cycle with a coefficient is visitCoef)
 	LevelHost &L = *g->levels[level];
 	int        rc;
 	const bool xfok = (L.dim == 3 && g->in_cycle); // outside te_vcycle nobody keeps xf_valid_for honest
@@ -402,6 +403,10 @@ static uint64_t optsKey(const te_cycle_opts *o)
 // te_vcycle; `pending`: f is still to be formed (te_bicgstab; consumed by level 0's first reader, visit())
 int vcycleWith(te_gmg *g, const te_cycle_opts *o, const te_vec *f, te_vec *u, const PendingRhs *pending)
 {
+	if (g && g->coef_on) { // a coefficient is set: the plain driver of gmg_coef.hip (te_bicgstab hands over no pending statement then)
+		if (pending) return te::fail(TE_ESTATE, "te_vcycle: a pending right-hand side with a coefficient set");
+		return vcycleCoef(g, o, f, u);
+	}
 	{
 	int rc;
 	if (!o) return te::fail(TE_EINVAL, "te_vcycle: null options");
@@ -450,6 +455,7 @@ int te_apply(te_gmg *g, int level, const te_vec *u, te_vec *f)
 		int rc;
 		if ((rc = checkLevelVec(g, level, u, "te_apply")) || (rc = checkLevelVec(g, level, f, "te_apply"))) return rc;
 		if (u == f) return te::fail(TE_EINVAL, "te_apply: in-place apply is not supported");
+		if (g->coef_on) return coefStencil(g, *g->levels[level], COEF_APPLY, u->d, nullptr, f->d, 0.0);
 		return launchStencil<MODE_APPLY>(g, *g->levels[level], u->d, nullptr, f->d, 0.0);
 	});
 }
@@ -462,6 +468,7 @@ int te_residual(te_gmg *g, int level, const te_vec *u, const te_vec *f, te_vec *
 		    || (rc = checkLevelVec(g, level, r, "te_residual")))
 			return rc;
 		if (u == r) return te::fail(TE_EINVAL, "te_residual: r must not alias u");
+		if (g->coef_on) return coefStencil(g, *g->levels[level], COEF_RESID, u->d, f->d, r->d, 0.0);
 		return launchStencil<MODE_RESID>(g, *g->levels[level], u->d, f->d, r->d, 0.0);
 	});
 }
@@ -476,6 +483,10 @@ int te_residual_norm_sq(te_gmg *g, int level, const te_vec *u, const te_vec *f, 
 			return rc;
 		if (u == r) return te::fail(TE_EINVAL, "te_residual_norm_sq: r must not alias u");
 		LevelHost &L = *g->levels[level];
+		if (g->coef_on) { // the residual of A_b, then a pass of its own over r
+			if ((rc = coefStencil(g, L, COEF_RESID, u->d, f->d, r->d, 0.0))) return rc;
+			return reduce<RED_SUMSQ>(r, nullptr, norm_sq);
+		}
 		if (L.dim == 2) { // (2D: the same kernel forms one partial sum per workgroup; a fixed grid, so a fixed order)
 			*norm_sq = 0.0;
 			if (L.P == 0) return TE_OK;
@@ -758,6 +769,7 @@ int te_patch_apply(te_gmg *g, int level, const te_vec *u, te_vec *f)
 	return guarded([&]() -> int {
 		int rc;
 		if ((rc = checkLevelVec(g, level, u, "te_patch_apply")) || (rc = checkLevelVec(g, level, f, "te_patch_apply"))) return rc;
+		if ((rc = coefRefuse(g, "te_patch_apply"))) return rc; // (the patch solves invert the constant-coefficient patch operator)
 		if (u == f) return te::fail(TE_EINVAL, "te_patch_apply: in-place apply is not supported");
 		return launchStencil<MODE_APPLY>(g, *g->levels[level], u->d, nullptr, f->d, 0.0, RestrictDst(), nullptr, RED_NONE, nullptr, nullptr, true);
 	});

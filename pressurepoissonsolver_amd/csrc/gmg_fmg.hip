@@ -48,6 +48,7 @@ int te_fmg(te_gmg *g, const te_cycle_opts *o, const te_vec *f, const te_vec *bda
 		if (f == u) return te::fail(TE_EINVAL, "te_fmg: f and u must be different vectors");
 		if (bdata && (bdata->g != g || bdata->level != 0 || !bdata->bnd)) return te::fail(TE_EINVAL, "te_fmg: bdata is not a boundary vector of level 0");
 		if (cycles < 0) return te::fail(TE_EINVAL, "te_fmg: cycles must not be negative");
+		if ((rc = coefRefuse(g, "te_fmg"))) return rc; // (the coarsest level's exact solve and the fold of boundary data are the Laplacian's)
 		if (g->nranks > 1)
 			return te::fail(TE_ESTATE, "te_fmg: not implemented on a sharded hierarchy (te_prolong_quadratic and te_boundary_restrict are single-rank); "
 			                           "te_bicgstab works there");

@@ -15,6 +15,7 @@
 //   gmg_fmg.hip        the full-multigrid solve te_fmg and its work vectors
 //   gmg_regrid.hip     the per-patch indicator te_patch_indicator and the transfer between two meshes te_vec_regrid (regridkernels.hpp)
 //   gmg_faceregrid.hip the transfer of a face vector between two meshes te_faces_regrid (faceregridkernels.hpp)
+//   gmg_coef.hip       the variable-coefficient operator div(beta grad u): coefficient per level, operator, sweeps, cycle (coefkernels.hpp)
 #pragma once
 #include "capi_common.hpp"
 #include "level_tables.hpp"
@@ -98,7 +99,10 @@ enum KClass : int {
 	KC_INDICATOR, KC_REGRID,
 	// the transfer of a face vector (faceregridkernels.hpp): per destination site at 32^3 (a cell, its three lower faces
 	// and its share of the HI blocks: 24.75 B) 49.5 B copied, 24.75 written + about 4 read refined, 24.75 + 99 coarsened
-	KC_FACE_REGRID, KC_COUNT
+	KC_FACE_REGRID,
+	// the variable-coefficient path (coefkernels.hpp): operator, residual, Jacobi, one RB-GS sweep (both colour launches), and the
+	// restriction of the coefficient (cells = coarse sites)
+	KC_APPLY_COEF, KC_RESID_COEF, KC_JACOBI_COEF, KC_RBGS_COEF, KC_FACES_RESTRICT, KC_COUNT
 };
 extern const char *kclassName[KC_COUNT]; // (gmg_core.hip)
 
@@ -423,6 +427,10 @@ struct te_gmg {
 	struct FmgWs   *fmg   = nullptr;  // te_fmg's work vectors (gmg_fmg.hip), made at its first call
 	struct SchurWs *schur = nullptr;  // the Schur route's device tables and work vectors (gmg_schur.hip), made at its first use
 	struct RegridWs *regrid = nullptr; // the indicator's device output and the transfer's map (gmg_regrid.hip), made at their first use
+	// te_gmg_set_coefficient (gmg_coef.hip): the solver's own copy of beta on every level, made at the first call and kept; coef_on:
+	// a coefficient is set -- te_apply, te_residual, te_smooth, te_vcycle and te_bicgstab take the variable-coefficient path
+	struct CoefWs *coef = nullptr;
+	bool           coef_on = false;
 	// level 0 = the leaves of the mesh: tree node id, tree parent, orthant there, lower corner and lengths per patch (host copies of
 	// the hierarchy's te_hier_leaf_tree / level tables, global order): what te_vec_regrid matches two meshes by
 	std::vector<int32_t> leaf_id, leaf_parent, leaf_orth;
@@ -729,6 +737,18 @@ void fmgFree(te_gmg *g); // (te_gmg_release_workspace, te_gmg_destroy)
 // ---- gmg_regrid.hip
 void regridFree(te_gmg *g); // (te_gmg_destroy)
 int  regridMapUpload(te_gmg *src, te_gmg *dst, const char *who, const int32_t **map_dev); // one row per patch of dst, in dst's buffer
+// ---- gmg_coef.hip (with a coefficient set: the operator A_b = div(beta grad .) in place of the Laplacian)
+void coefFree(te_gmg *g); // (te_gmg_destroy; te_gmg_release_workspace while no coefficient is set)
+int  coefStencil(te_gmg *g, LevelHost &L, int mode, const double *u, const double *f, double *out, double omega); // mode: coefkernels.hpp CoefMode
+int  coefSmoothOnce(te_gmg *g, int level, const te_vec *f, te_vec *u, int smoother, double omega);
+int  vcycleCoef(te_gmg *g, const te_cycle_opts *o, const te_vec *f, te_vec *u); // te_vcycle with a coefficient (visitCoef)
+// the calls that have no variable-coefficient form: TE_ESTATE while one is set
+inline int coefRefuse(const te_gmg *g, const char *who)
+{
+	if (g && g->coef_on)
+		return te::fail(TE_ESTATE, std::string(who) + ": not available while a coefficient is set (te_gmg_set_coefficient(g, NULL) clears it)");
+	return TE_OK;
+}
 // ---- gmg_launch2d.hip
 int prepareGhosts2d(te_gmg *g, LevelHost &L, const double *u, bool patch_op = false);
 template <int MODE> int launchStencil2d(te_gmg *g, LevelHost &L, const double *u, const double *f, double *out, double omega, int redmode = RED_NONE,

@@ -31,6 +31,7 @@ int te_vec_scale_then_add_scaled2(te_vec *v, double a, double be, const te_vec *
 		return vecop<VOP_SCALE_THEN_ADD_SCALED2>(v, b, c, a, be, ga);
 	});
 }
+int te_vec_multiply(te_vec *v, const te_vec *b) { return guarded([&]() -> int { return vecop<VOP_MULTIPLY>(v, b, nullptr, 0, 0, 0); }); }
 int te_vec_two_norm_sq(const te_vec *v, double *out) { return guarded([&]() -> int { return reduce<RED_SUMSQ>(v, nullptr, out); }); }
 int te_vec_inf_norm(const te_vec *v, double *out) { return guarded([&]() -> int { return reduce<RED_MAXABS>(v, nullptr, out); }); }
 int te_vec_dot(const te_vec *v, const te_vec *b, double *out) { return guarded([&]() -> int { return reduce<RED_DOT>(v, b, out); }); }
@@ -91,7 +92,8 @@ int te_bicgstab(te_gmg *g, const te_cycle_opts *o, te_vec *x, const te_vec *b, i
 		// same box, alternating) the fused form is SLOWER, 9.33 -> 9.60 ms per solve -- the vectors of a 2D problem that size sit in
 		// the Infinity Cache, where a separate dot-product pass costs less than the second operand and the block sums cost the
 		// stencil kernel.
-		const bool   fused = g->dim == 3 && !g->cfg.has(O_NO_BICG_FUSE);
+		// With a coefficient (te_gmg_set_coefficient) the separate passes as well: te_apply is A_b, te_vcycle the plain driver visitCoef.
+		const bool   fused = g->dim == 3 && !g->cfg.has(O_NO_BICG_FUSE) && !g->coef_on;
 		g->keep_final_xf   = fused && o != nullptr && !g->cfg.has(O_NO_XF) && !g->cfg.has(O_NO_BICG_XF);
 		LevelHost   &L0    = *g->levels[0];
 		const size_t n2    = x->n / 2;

@@ -285,8 +285,8 @@ static int bicgstabS(te_gmg *g, LevelHost &L, SchurLevel &S, bool cheb, te_vec *
 static int enter(te_gmg *g, int level, const char *who, LevelHost **L, SchurLevel **S)
 {
 	if (!g || level < 0 || level >= (int) g->levels.size()) return te::fail(TE_EINVAL, std::string(who) + ": bad level");
-	int rc = schurLevel(g, level, S);
-	if (rc) return rc;
+	int rc = coefRefuse(g, who); // (the Schur route's patch solves invert the constant-coefficient patch operator)
+	if (rc || (rc = schurLevel(g, level, S))) return rc;
 	*L = g->levels[level].get();
 	(*L)->xf_valid_for = nullptr; // (the level's scratch is rewritten)
 	return TE_OK;

@@ -21,6 +21,7 @@
 namespace te
 {
 enum StencilMode : int { MODE_APPLY = 0, MODE_RESID = 1, MODE_JACOBI = 2, MODE_RESID_RESTRICT = 3 };
+enum CoefMode : int { COEF_APPLY = 0, COEF_RESID = 1, COEF_JACOBI = 2 }; // the same three of the variable-coefficient operator (coefkernels.hpp)
 
 // where the fused residual+restriction kernel puts the coarse right-hand side of a patch:
 // parent[p] >= 0: octant orth[p] of that coarse patch; parent[p] <= -2: block -(parent+2) of `remote`
@@ -647,7 +648,8 @@ __global__ __launch_bounds__(256) void k_dst_axis3d(int P, const int32_t *__rest
 // ---- BLAS-1 (Vector.h:190-321) ------------------------------------------------------------------
 enum VecOp : int {
 	VOP_SET, VOP_SCALE, VOP_SHIFT, VOP_COPY, VOP_ADD, VOP_ADD_SCALED, VOP_ADD_SCALED2,
-	VOP_SCALE_THEN_ADD, VOP_SCALE_THEN_ADD_SCALED, VOP_SCALE_THEN_ADD_SCALED2
+	VOP_SCALE_THEN_ADD, VOP_SCALE_THEN_ADD_SCALED, VOP_SCALE_THEN_ADD_SCALED2,
+	VOP_MULTIPLY // v[i] *= a[i] (te_vec_multiply; nothing in Vector.h)
 };
 template <int OP>
 __global__ __launch_bounds__(256) void k_vecop(size_t n2, double2 *__restrict__ v, const double2 *__restrict__ a,
@@ -682,6 +684,7 @@ __global__ __launch_bounds__(256) void k_vecop(size_t n2, double2 *__restrict__ 
 					r.x = alpha * r.x + beta * av.x + gamma * bv.x;
 					r.y = alpha * r.y + beta * av.y + gamma * bv.y;
 					break;
+				case VOP_MULTIPLY: r.x *= av.x; r.y *= av.y; break;
 				default: break;
 			}
 		}
