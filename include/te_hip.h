@@ -407,6 +407,16 @@ int te_faces_regrid(te_gmg *src, const te_vec *U_src, te_gmg *dst, te_vec *U_dst
  * for the few that shape the level tables and are therefore fixed at creation; TE_EINVAL for an unknown name. */
 int te_gmg_set_option(te_gmg *g, const char *name, const char *value);
 
+/* The number of z-slabs per patch that the 3D kernels of `level` run with right now -- the switches as they stand, TE_ZS_PIN
+ * included. kind: TE_SLABS_STENCIL for the operator, residual and Jacobi kernels, the MAC operators, the interpolators, the
+ * indicator and the regrid transfers; TE_SLABS_SWEEP for the RB-GS sweeps over the whole level (a launch over a part of the level,
+ * as under an overlapped exchange, is ruled by the number of patches of that part). A 2D level has no slabs: 1. TE_EINVAL for
+ * NULL, a level that does not exist or another kind.
+ * TE_ZS_PIN = 1, 2, 4 or 8 (anything else: TE_EINVAL from te_gmg_set_option and from te_gmg_create) replaces both rules by that
+ * count, clamped down to the largest one the patch size admits (n / count >= 4), whatever the number of patches. */
+enum { TE_SLABS_STENCIL = 0, TE_SLABS_SWEEP = 1 };
+int te_gmg_slab_count(const te_gmg *g, int level, int kind, int *zs);
+
 /* ------------------------------------------------------------ multi-rank ghost exchange */
 /* The library never talks to the network itself. When a level has off-rank neighbours, it
  * packs the needed face layers into one send buffer, calls `exchange`, and reads the receive

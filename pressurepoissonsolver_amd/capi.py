@@ -31,6 +31,7 @@ SMOOTH_PATCH_SOLVE, SMOOTH_JACOBI, SMOOTH_RBGS, SMOOTH_PATCH_BCGS = 0, 1, 2, 3
 PROBLEM_TRIG, PROBLEM_GAUSS, PROBLEM_RANDOM = 0, 1, 2
 SCHUR_PREC_NONE, SCHUR_PREC_CHEB = 0, 1
 INTERP_DIRECT, INTERP_LINEAR = 0, 1  # TE_INTERP_*: DrctIntp (the default), tri-/bilinear
+SLABS_STENCIL, SLABS_SWEEP = 0, 1  # TE_SLABS_*: which slab rule te_gmg_slab_count reports
 
 
 class CycleOpts(C.Structure):
@@ -139,6 +140,7 @@ SYMBOLS = {
     "te_bicgstab": (_I, [_P, C.POINTER(CycleOpts), _P, _P, _I, _D, C.POINTER(_I), _PD]),
     "te_gmg_release_workspace": (_I, [_P]),
     "te_gmg_set_option": (_I, [_P, C.c_char_p, C.c_char_p]),
+    "te_gmg_slab_count": (_I, [_P, _I, _I, _P]),
     "te_gmg_set_exchange": (_I, [_P, EXCHANGE_FN, _P]),
     "te_rccl_unique_id": (_I, [C.c_char_p, C.c_char_p]),
     "te_gmg_use_rccl": (_I, [_P, C.c_char_p, C.c_char_p, _I, _I]),
@@ -693,6 +695,12 @@ class GMG:
     def set_option(self, name, value="1"):
         """one TE_* switch of this solver (they are read from the environment once, at creation); None clears it"""
         check(lib().te_gmg_set_option(self.h, name.encode(), None if value is None else str(value).encode()))
+
+    def slab_count(self, level, kind=0):
+        """z-slabs per patch of the 3D kernels of `level` as the switches stand (SLABS_STENCIL or SLABS_SWEEP)"""
+        zs = C.c_int()
+        check(lib().te_gmg_slab_count(self.h, level, kind, C.byref(zs)))
+        return zs.value
 
     def release_workspace(self):
         """hand te_bicgstab's work vectors (8 x a level-0 vector) and te_fmg's back"""

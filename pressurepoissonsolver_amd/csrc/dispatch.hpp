@@ -1,7 +1,8 @@
-// From a run-time patch size / z-slab count to the template instantiation of a 3D launch: the one place that maps them (see
-// gmg_ghosts3d.hpp for the slab rules and the grid). Plain C++17, no HIP header: tests/dispatch_host.cpp builds it with a host
-// compiler alone.
+// From a run-time patch size / z-slab count to the template instantiation of a 3D launch: the one place that maps them, and the
+// rules that choose the slab count (see gmg_ghosts3d.hpp for the grid). Plain C++17, no HIP header: tests/dispatch_host.cpp
+// builds it with a host compiler alone.
 #pragma once
+#include <cstddef>
 #include <type_traits>
 
 namespace tei
@@ -34,5 +35,46 @@ template <int N, class F> inline void dispatchSlabs(int slabs, F f)
 			if constexpr (N >= 16) f(std::integral_constant<int, 4>{});
 			break;
 	}
+}
+
+// The slab rules as plain arithmetic (gmg_ghosts3d.hpp stencilSlabs<N> / rbgsSlabs<N> read the switches from the solver and call
+// these; te_gmg_slab_count reports them). SlabSwitches::pin (TE_ZS_PIN: 0 = not set, else 1, 2, 4 or 8) overrides both rules
+// whatever the patch count: the pinned count, clamped down to the largest one the patch size admits -- never a count that
+// dispatchSlabs<N> would drop.
+struct SlabSwitches {
+	bool zs_force = false, rbgs_noslab = false, no_zs8 = false; // TE_ZS_FORCE, TE_RBGS_NOSLAB, TE_NO_ZS8
+	int  pin = 0;
+};
+
+// the largest slab count a patch of size n admits: a slab is at least four planes thick, and no kernel has more than eight
+inline int maxSlabs(int n) { return n >= 32 ? 8 : (n >= 16 ? 4 : (n >= 8 ? 2 : 1)); }
+
+inline bool slabPinValid(int pin) { return pin == 1 || pin == 2 || pin == 4 || pin == 8; }
+
+inline int pinnedSlabs(int n, int pin) { return pin < maxSlabs(n) ? pin : maxSlabs(n); }
+
+// z-slabs per patch for the stencil kernels (and the MAC operators, the interpolators, the regrid transfer): enough workgroups to
+// fill 256 CUs a few times over when the level has few patches
+inline int stencilSlabCount(int n, int P, const SlabSwitches &s)
+{
+	if (s.pin) return pinnedSlabs(n, s.pin);
+	int zs = 1;
+	if (n >= 8) {
+		while (zs < 4 && (s.zs_force || (size_t) P * zs < 2048) && n / (zs * 2) >= 4) zs *= 2;
+		if (zs == 4 && n == 32 && P <= 64 && !s.no_zs8) zs = 8; // (see rbgsSlabCount)
+	}
+	return zs;
+}
+
+// z-slabs per patch for the RB-GS kernels: enough workgroups to occupy 256 CUs x 4 when the level has few patches
+inline int rbgsSlabCount(int n, int count, const SlabSwitches &s)
+{
+	if (s.pin) return pinnedSlabs(n, s.pin);
+	int zs = 1;
+	while (zs < 4 && !s.rbgs_noslab && (size_t) count * zs < 1024 && n / (zs * 2) >= 4) zs *= 2;
+	// very few patches (the coarsest levels of a cycle): a kernel is one patch's march, a dependent chain of plane steps of
+	// ~1-2 us each that nothing hides -- eight slabs of four planes (six steps) instead of four of eight (ten steps)
+	if (zs == 4 && n == 32 && count <= 64 && !s.no_zs8) zs = 8;
+	return zs;
 }
 } // namespace tei

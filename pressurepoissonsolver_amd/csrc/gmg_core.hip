@@ -15,7 +15,7 @@ const char *kclassName[KC_COUNT] = {"stencil_apply", "stencil_resid", "stencil_j
 const char *optName[O_COUNT] = {"TE_2D_SIMPLE", "TE_2D_NO_MFMA", "TE_2D_NO_PF", "TE_2D_NO_MR_FUSE", "TE_2D_TPB", "TE_NO_FUSE2", "TE_NO_FUSE3",
                                 "TE_NO_FUSE3_CF", "TE_NO_CFP", "TE_NO_XF", "TE_NO_FCORR", "TE_NO_FCORR_CF", "TE_NO_GTAB", "TE_NO_OVERLAP",
                                 "TE_OVERLAP_MIN", "TE_NO_PS_FACES", "TE_PS_MODE", "TE_PS_SLOW", "TE_RBGS_NOSLAB", "TE_ZS_FORCE", "TE_NO_ZS8",
-                                "TE_RESWEEP_V", "TE_EXCHANGE_TIMEOUT", "TE_NO_VERIFY", "TE_RCCL_LOOPBACK", "TE_ZR_AHEAD", "TE_NO_BICG_FUSE", "TE_POST_EXCHANGE", "TE_REPL_BLOCKS", "TE_PACK_FACES", "TE_OVERLAP_MODE", "TE_PUSH_TIMEOUT", "TE_NO_BICG_XF", "TE_PUSH_FAULT", "TE_2D_NO_FOLD", "TE_2D_NO_SYM", "TE_PUSH_NONFATAL", "TE_PS_NO_HALF", "TE_PS_HALF_MAX", "TE_NO_GTAB2", "TE_NO_RS6_CF", "TE_NO_RS6_FIXUP", "TE_NO_CFP59", "TE_SCHUR_FULL"};
+                                "TE_RESWEEP_V", "TE_EXCHANGE_TIMEOUT", "TE_NO_VERIFY", "TE_RCCL_LOOPBACK", "TE_ZR_AHEAD", "TE_NO_BICG_FUSE", "TE_POST_EXCHANGE", "TE_REPL_BLOCKS", "TE_PACK_FACES", "TE_OVERLAP_MODE", "TE_PUSH_TIMEOUT", "TE_NO_BICG_XF", "TE_PUSH_FAULT", "TE_2D_NO_FOLD", "TE_2D_NO_SYM", "TE_PUSH_NONFATAL", "TE_PS_NO_HALF", "TE_PS_HALF_MAX", "TE_NO_GTAB2", "TE_NO_RS6_CF", "TE_NO_RS6_FIXUP", "TE_NO_CFP59", "TE_SCHUR_FULL", "TE_ZS_PIN"};
 
 void drainEvents(te_gmg *g)
 {
@@ -34,6 +34,14 @@ void drainEvents(te_gmg *g)
 void Cfg::fromEnv()
 {
 	for (int o = 0; o < O_COUNT; o++) set(o, getenv(optName[o]));
+}
+
+// the value of TE_ZS_PIN: "1", "2", "4" or "8" and nothing else (0: not one of them)
+static int parseSlabPin(const char *v)
+{
+	if (!v || !v[0] || v[1]) return 0;
+	const int pin = v[0] - '0';
+	return slabPinValid(pin) ? pin : 0;
 }
 
 // places the tables of level li (level_tables.cpp) on the device; the order of the allocations is part of the set-up's behaviour
@@ -174,11 +182,13 @@ int te_gmg_create(const te_hier *h, int device, te_gmg **out)
 		memset(g->calls, 0, sizeof(g->calls));
 		memset(g->cells, 0, sizeof(g->cells));
 		memset(g->total_ms, 0, sizeof(g->total_ms));
+		g->cfg.fromEnv();
+		if (g->cfg.has(O_ZS_PIN) && !(g->zs_pin = parseSlabPin(g->cfg.str(O_ZS_PIN)))) // (before the solver owns anything)
+			return te::fail(TE_EINVAL, "te_gmg_create: TE_ZS_PIN must be 1, 2, 4 or 8");
 		HIPCHK(hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking));
 		HIPCHK(hipStreamCreateWithFlags(&g->comm_stream, hipStreamNonBlocking));
 		HIPCHK(hipEventCreateWithFlags(&g->ev_pack, hipEventDisableTiming));
 		HIPCHK(hipEventCreateWithFlags(&g->ev_recv, hipEventDisableTiming));
-		g->cfg.fromEnv();
 		g->overlap = !g->cfg.has(O_NO_OVERLAP);
 		const auto t_ctx = clk::now();
 		int rc;
@@ -186,9 +196,12 @@ int te_gmg_create(const te_hier *h, int device, te_gmg **out)
 			if ((rc = buildLevel(g.get(), h->h, li))) return rc;
 		const auto     t_levels = clk::now();
 		const SetupAcc acc_levels = acc;
-		{ // partial sums: the reduction kernels' blocks, or one pair per work item of a stencil launch with fused sums (<= 8 slabs per patch)
+		{ // partial sums: the reduction kernels' blocks, or one pair per work item of a stencil launch with fused sums. A 3D level
+			// gets room for the largest slab count its patch size admits (dispatch.hpp maxSlabs), whatever the rule gives it now:
+			// no switch set later (TE_ZS_FORCE, TE_ZS_PIN) can ask for more
 			size_t items = (size_t) g->red_blocks;
-			for (auto &L : g->levels) items = std::max(items, (size_t) L->P * (L->P <= 64 ? 8 : (L->P < 2048 ? 4 : 1)));
+			for (auto &L : g->levels)
+				if (L->dim == 3) items = std::max(items, (size_t) L->P * maxSlabs(L->n));
 			// 2D: one pair per workgroup of k_stencil2d's FLAT grid (one x-pair per thread: a capped grid-stride loop streams a third
 			// slower on this chip and cost the fused sums more than the passes they replace)
 			for (auto &L : g->levels)
@@ -586,12 +599,32 @@ int te_gmg_set_option(te_gmg *g, const char *name, const char *value)
 				if (!strcmp(name, optName[o])) {
 					if (optStructural(o))
 						return te::fail(TE_ESTATE, std::string("te_gmg_set_option: ") + name + " is read when the solver is created; set it in the environment before te_gmg_create");
+					if (o == O_ZS_PIN) {
+						const int pin = parseSlabPin(value);
+						if (value && !pin) return te::fail(TE_EINVAL, "te_gmg_set_option: TE_ZS_PIN must be 1, 2, 4 or 8");
+						g->zs_pin = pin;
+					}
 					g->cfg.set(o, value);
 					if (o == O_PUSH_TIMEOUT) g->push.timeout_s = value ? std::max(0.1, atof(value)) : (g->wd.timeout_s > 0 ? g->wd.timeout_s : 300.0);
 					g->verified_opts.clear(); // (an option may change which exchanges a cycle issues)
 					return TE_OK;
 				}
 			return te::fail(TE_EINVAL, std::string("te_gmg_set_option: unknown option ") + name);
+	});
+}
+
+// what stencilSlabs<N> / rbgsSlabs<N> (gmg_ghosts3d.hpp) give a launch over the whole level as the switches stand
+int te_gmg_slab_count(const te_gmg *g, int level, int kind, int *zs)
+{
+	return guarded([&]() -> int {
+			if (!g || !zs || level < 0 || level >= (int) g->levels.size() || (kind != TE_SLABS_STENCIL && kind != TE_SLABS_SWEEP))
+				return te::fail(TE_EINVAL, "te_gmg_slab_count: bad argument");
+			const LevelHost &L = *g->levels[level];
+			if (L.dim != 3)
+				*zs = 1;
+			else
+				*zs = kind == TE_SLABS_STENCIL ? stencilSlabCount(L.n, L.P, slabSwitches(g)) : rbgsSlabCount(L.n, L.P, slabSwitches(g));
+			return TE_OK;
 	});
 }
 } // extern "C"

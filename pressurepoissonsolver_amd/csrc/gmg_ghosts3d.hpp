@@ -138,26 +138,12 @@ template <int N, class F> int withGhosts(te_gmg *g, LevelHost &L, const GhostSrc
 
 // z-slabs per patch for the stencil kernels (and the MAC operators, the interpolators, the regrid transfer): enough workgroups to
 // fill 256 CUs a few times over when the level has few patches
-template <int N> inline int stencilSlabs(const te_gmg *g, int P)
-{
-	int zs = 1;
-	if (N >= 8) {
-		while (zs < 4 && (g->cfg.has(O_ZS_FORCE) || (size_t) P * zs < 2048) && N / (zs * 2) >= 4) zs *= 2;
-		if (zs == 4 && N == 32 && P <= 64 && !g->cfg.has(O_NO_ZS8)) zs = 8; // (see rbgsSlabs)
-	}
-	return zs;
-}
+// (the rule itself is dispatch.hpp stencilSlabCount; this reads the solver's switches)
+template <int N> inline int stencilSlabs(const te_gmg *g, int P) { return stencilSlabCount(N, P, slabSwitches(g)); }
 
 // z-slabs per patch for the RB-GS kernels: enough workgroups to occupy 256 CUs x 4 when the level has few patches
-template <int N> inline int rbgsSlabs(const te_gmg *g, int count)
-{
-	int zs = 1;
-	while (zs < 4 && !g->cfg.has(O_RBGS_NOSLAB) && (size_t) count * zs < 1024 && N / (zs * 2) >= 4) zs *= 2;
-	// very few patches (the coarsest levels of a cycle): a kernel is one patch's march, a dependent chain of plane steps of
-	// ~1-2 us each that nothing hides -- eight slabs of four planes (six steps) instead of four of eight (ten steps)
-	if (zs == 4 && N == 32 && count <= 64 && !g->cfg.has(O_NO_ZS8)) zs = 8;
-	return zs;
-}
+// (dispatch.hpp rbgsSlabCount)
+template <int N> inline int rbgsSlabs(const te_gmg *g, int count) { return rbgsSlabCount(N, count, slabSwitches(g)); }
 
 // the grid of a launch over `count` patches in `zs` slabs each with Tile3<N>::TPB threads: whole multiples of eight workgroups
 inline dim3 slabGrid(int count, int zs = 1) { return dim3(8 * ((count * zs + 7) / 8)); }

@@ -18,6 +18,7 @@
 //   gmg_coef.hip       the variable-coefficient operator div(beta grad u): coefficient per level, operator, sweeps, cycle (coefkernels.hpp)
 #pragma once
 #include "capi_common.hpp"
+#include "dispatch.hpp"
 #include "level_tables.hpp"
 #include <hip/hip_ext.h>
 #include <rccl/rccl.h> // enum values and ncclUniqueId only: the library itself is dlopen'ed (te_gmg_use_rccl)
@@ -112,7 +113,7 @@ extern const char *kclassName[KC_COUNT]; // (gmg_core.hip)
 enum Opt : int {
 	O_2D_SIMPLE, O_2D_NO_MFMA, O_2D_NO_PF, O_2D_NO_MR_FUSE, O_2D_TPB, O_NO_FUSE2, O_NO_FUSE3, O_NO_FUSE3_CF, O_NO_CFP, O_NO_XF,
 	O_NO_FCORR, O_NO_FCORR_CF, O_NO_GTAB, O_NO_OVERLAP, O_OVERLAP_MIN, O_NO_PS_FACES, O_PS_MODE, O_PS_SLOW, O_RBGS_NOSLAB,
-	O_ZS_FORCE, O_NO_ZS8, O_RESWEEP_V, O_EXCHANGE_TIMEOUT, O_NO_VERIFY, O_RCCL_LOOPBACK, O_ZR_AHEAD, O_NO_BICG_FUSE, O_POST_EXCHANGE, O_REPL_BLOCKS, O_PACK_FACES, O_OVERLAP_MODE, O_PUSH_TIMEOUT, O_NO_BICG_XF, O_PUSH_FAULT, O_2D_NO_FOLD, O_2D_NO_SYM, O_PUSH_NONFATAL, O_PS_NO_HALF, O_PS_HALF_MAX, O_NO_GTAB2, O_NO_RS6_CF, O_NO_RS6_FIXUP, O_NO_CFP59, O_SCHUR_FULL, O_COUNT
+	O_ZS_FORCE, O_NO_ZS8, O_RESWEEP_V, O_EXCHANGE_TIMEOUT, O_NO_VERIFY, O_RCCL_LOOPBACK, O_ZR_AHEAD, O_NO_BICG_FUSE, O_POST_EXCHANGE, O_REPL_BLOCKS, O_PACK_FACES, O_OVERLAP_MODE, O_PUSH_TIMEOUT, O_NO_BICG_XF, O_PUSH_FAULT, O_2D_NO_FOLD, O_2D_NO_SYM, O_PUSH_NONFATAL, O_PS_NO_HALF, O_PS_HALF_MAX, O_NO_GTAB2, O_NO_RS6_CF, O_NO_RS6_FIXUP, O_NO_CFP59, O_SCHUR_FULL, O_ZS_PIN, O_COUNT
 };
 extern const char *optName[O_COUNT]; // (gmg_core.hip)
 // options that shape the level tables te_gmg_create builds: fixed for the solver's lifetime
@@ -397,6 +398,7 @@ using namespace tei;
 
 struct te_gmg {
 	Cfg                                     cfg; // the TE_* switches, read once in te_gmg_create
+	int                                     zs_pin = 0; // TE_ZS_PIN as a number (0: not set); te_gmg_create and te_gmg_set_option validate and keep it
 	int                                     device = 0;
 	hipStream_t                             stream = nullptr;
 	// ghost exchanges run on their own stream so that interior patches compute underneath them
@@ -530,6 +532,17 @@ struct te_gmg {
 
 namespace tei
 {
+// what the slab rules (dispatch.hpp) read of a solver
+inline SlabSwitches slabSwitches(const te_gmg *g)
+{
+	SlabSwitches s;
+	s.zs_force    = g->cfg.has(O_ZS_FORCE);
+	s.rbgs_noslab = g->cfg.has(O_RBGS_NOSLAB);
+	s.no_zs8      = g->cfg.has(O_NO_ZS8);
+	s.pin         = g->zs_pin;
+	return s;
+}
+
 struct Timed {
 	te_gmg *g;
 	int     idx = -1;

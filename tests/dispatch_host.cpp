@@ -1,5 +1,8 @@
 // Stand-alone host check of csrc/dispatch.hpp (tests/test_dispatch_host.py builds it with g++ and the sanitizers): dispatchN maps
-// a run-time patch size, dispatchSlabs<N> a run-time slab count, to the integral constant the launch sites instantiate with.
+// a run-time patch size, dispatchSlabs<N> a run-time slab count, to the integral constant the launch sites instantiate with;
+// stencilSlabCount / rbgsSlabCount choose that count -- for every patch size, 1 ... 5000 patches, every combination of
+// TE_ZS_FORCE / TE_RBGS_NOSLAB / TE_NO_ZS8 and every TE_ZS_PIN they return a count dispatchSlabs<N> runs (never one it drops),
+// the written-out table without a pin, min(pin, largest admitted) with one.
 #include "dispatch.hpp"
 #include <cstdio>
 #include <initializer_list>
@@ -35,6 +38,71 @@ template <int N> void checkSlabs()
 			check(calls == 0, "dispatchSlabs: no call for a forbidden pair", N, zs);
 	}
 }
+
+// how often dispatchSlabs<N> runs its functor for `zs`, and with which ZS
+template <int N> int dispatched(int zs, int &got)
+{
+	int calls = 0;
+	got       = -1;
+	tei::dispatchSlabs<N>(zs, [&](auto z) {
+		calls++;
+		got = decltype(z)::value;
+	});
+	return calls;
+}
+
+// The rules without a pin, written out as tables of thresholds (from the loops of stencilSlabCount / rbgsSlabCount as they stood
+// when the rules moved into dispatch.hpp): doubling stops where count * zs reaches 2048 (stencil) or 1024 (sweep), so four slabs
+// need count * 2 below that, and eight go to 32^3 patches on levels of at most 64.
+int stencilTable(int n, int P, bool force, bool no_zs8)
+{
+	if (n == 4) return 1;
+	if (n == 8) return (force || P < 2048) ? 2 : 1;
+	const int zs = force ? 4 : (P < 1024 ? 4 : (P < 2048 ? 2 : 1));
+	return (n == 32 && zs == 4 && P <= 64 && !no_zs8) ? 8 : zs;
+}
+
+int sweepTable(int n, int count, bool noslab, bool no_zs8)
+{
+	if (n == 4 || noslab) return 1;
+	if (n == 8) return count < 1024 ? 2 : 1;
+	const int zs = count < 512 ? 4 : (count < 1024 ? 2 : 1);
+	return (n == 32 && zs == 4 && count <= 64 && !no_zs8) ? 8 : zs;
+}
+
+// the largest count a patch of size n admits, by the definition (a slab is at least four planes thick; at most eight slabs)
+int largestAdmitted(int n)
+{
+	int zs = 1;
+	while (zs < 8 && n / (zs * 2) >= 4) zs *= 2;
+	return zs;
+}
+
+template <int N> void checkRules()
+{
+	check(tei::maxSlabs(N) == largestAdmitted(N), "maxSlabs: the largest admitted count", N, tei::maxSlabs(N));
+	for (int sw = 0; sw < 8; sw++)
+		for (int pin : {0, 1, 2, 4, 8}) {
+			tei::SlabSwitches s;
+			s.zs_force = sw & 1, s.rbgs_noslab = sw & 2, s.no_zs8 = sw & 4, s.pin = pin;
+			for (int count = 1; count <= 5000; count++) {
+				const int st = tei::stencilSlabCount(N, count, s), rb = tei::rbgsSlabCount(N, count, s);
+				int       got;
+				check(dispatched<N>(st, got) == 1 && got == st, "stencil rule: a count dispatchSlabs runs exactly once", N, count);
+				check(dispatched<N>(rb, got) == 1 && got == rb, "sweep rule: a count dispatchSlabs runs exactly once", N, count);
+				if (pin) {
+					const int want = pin < largestAdmitted(N) ? pin : largestAdmitted(N);
+					check(st == want, "stencil rule: min(pin, largest admitted)", N, count);
+					check(rb == want, "sweep rule: min(pin, largest admitted)", N, count);
+				} else {
+					check(st == stencilTable(N, count, s.zs_force, s.no_zs8), "stencil rule: the table", N, count);
+					check(rb == sweepTable(N, count, s.rbgs_noslab, s.no_zs8), "sweep rule: the table", N, count);
+				}
+			}
+		}
+	for (int pin = -2; pin <= 20; pin++)
+		check(tei::slabPinValid(pin) == (pin == 1 || pin == 2 || pin == 4 || pin == 8), "slabPinValid", N, pin);
+}
 } // namespace
 
 int main()
@@ -60,6 +128,10 @@ int main()
 	checkSlabs<8>();
 	checkSlabs<16>();
 	checkSlabs<32>();
+	checkRules<4>();
+	checkRules<8>();
+	checkRules<16>();
+	checkRules<32>();
 	if (failures) return 1;
 	std::printf("DISPATCH_OK\n");
 	return 0;

@@ -18,7 +18,8 @@ pytestmark = pytest.mark.gpu
 
 # (mesh, n, divides, dim): the shapes of tests/test_gpu_regrid.py -- the smallest patch, a z-slab size with several blocks, the
 # production patch size (64 patches of 32^3 after +1: eight slabs), trees at a four-slab size and five levels deep, the 2D kernel on a
-# tree and at 64^2. One slab per patch needs 2048 patches or more: test_one_slab_per_patch below.
+# tree and at 64^2. One slab per patch: the rule gives it from 2048 patches on (test_one_slab_per_patch below); on few patches TE_ZS_PIN
+# gives it and every other admitted count (tests/test_gpu_slab_matrix.py).
 SHAPES = [("uniform", 4, 2, 3), ("uniform", 8, 2, 3), ("uniform", 32, 1, 3), ("2refine.bin", 16, 0, 3), ("multi_refine.bin", 8, 0, 3),
           ("2d2ref.bin", 4, 0, 2), ("uniform", 64, 2, 2)]
 IDS = lambda c: f"{c[0]}-n{c[1]}-d{c[2]}-{c[3]}d"  # noqa: E731
