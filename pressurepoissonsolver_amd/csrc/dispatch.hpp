@@ -1,5 +1,5 @@
 // From a run-time patch size / z-slab count to the template instantiation of a 3D launch: the one place that maps them, and the
-// rules that choose the slab count (see gmg_ghosts3d.hpp for the grid). Plain C++17, no HIP header: tests/dispatch_host.cpp
+// rules that choose the slab count (see gmg_ghosts3d.hpp for the grid) and the post-sweep's variant. Plain C++17, no HIP header: tests/dispatch_host.cpp
 // builds it with a host compiler alone.
 #pragma once
 #include <cstddef>
@@ -16,6 +16,12 @@ template <class F> inline auto dispatchN(int n, F f)
 		case 16: return f(std::integral_constant<int, 16>{});
 		default: return f(std::integral_constant<int, 32>{});
 	}
+}
+
+// f(std::bool_constant<b>) for a run-time flag that is a template argument of the launch
+template <class F> inline auto dispatchBool(bool b, F f)
+{
+	return b ? f(std::true_type{}) : f(std::false_type{});
 }
 
 // f(std::integral_constant<int, ZS>) for the slab count of a patch of size N: 1, 2 (N >= 8), 8 (N >= 32), anything else is 4
@@ -76,5 +82,28 @@ inline int rbgsSlabCount(int n, int count, const SlabSwitches &s)
 	// ~1-2 us each that nothing hides -- eight slabs of four planes (six steps) instead of four of eight (ten steps)
 	if (zs == 4 && n == 32 && count <= 64 && !s.no_zs8) zs = 8;
 	return zs;
+}
+
+// Which variant V of the recomputing post-sweep (march3d.hpp k_rbgs_resweep_prolong3d<N, V, FCORR, CFP>; all bit-identical) a
+// level runs. Each default was measured:
+//   * exported_terms (the level's right-hand side carries ghost terms: FCORR; level 1 of 512^3): 3, ordinary loads and stores --
+//     its u is the correction the finer level's post-sweep reads next (64.5 us, against 68.7 with non-temporal stores);
+//   * a coarser level otherwise: 27, non-temporal loads of f and stores of u;
+//   * the finest level stores u non-temporally (nobody re-reads it) and loads f non-temporally unless f can still be in the
+//     Infinity Cache from the pre-sweep that read it -- up to 160 MiB: 19 (256^3, a rank's share at eight ranks; 53.4 -> 49.0 us
+//     at 256^3); a larger one runs two workgroups per CU with four planes of f in flight each instead of three with two: 59
+//     (450 -> 443 us at 512^3; slower at 256^3).
+// refined (CFP: copy-through patches / coarse-fine ghost slots) has no 19: it runs 27. pin (TE_RESWEEP_V: 0 = not set, else 19,
+// 27 or 59) replaces the default on levels without exported terms -- how a small test shape reaches the kernel of a large level.
+// 0: no such kernel -- a level with exported terms is never a refined one.
+constexpr size_t kResweepCacheBytes = (size_t) 160 << 20;
+
+inline bool resweepPinValid(int pin) { return pin == 19 || pin == 27 || pin == 59; }
+
+inline int resweepVariant(bool exported_terms, bool refined, int index, size_t level_bytes, int pin)
+{
+	if (exported_terms) return refined ? 0 : 3;
+	const int v = pin ? pin : (index != 0 ? 27 : (level_bytes <= kResweepCacheBytes ? 19 : 59));
+	return (refined && v == 19) ? 27 : v;
 }
 } // namespace tei

@@ -13,9 +13,9 @@ const char *kclassName[KC_COUNT] = {"stencil_apply", "stencil_resid", "stencil_j
                                     "indicator", "regrid", "regrid_faces",
                                     "apply_coef", "resid_coef", "jacobi_coef", "rbgs_coef", "faces_restrict"};
 const char *optName[O_COUNT] = {"TE_2D_SIMPLE", "TE_2D_NO_MFMA", "TE_2D_NO_PF", "TE_2D_NO_MR_FUSE", "TE_2D_TPB", "TE_NO_FUSE2", "TE_NO_FUSE3",
-                                "TE_NO_FUSE3_CF", "TE_NO_CFP", "TE_NO_XF", "TE_NO_FCORR", "TE_NO_FCORR_CF", "TE_NO_GTAB", "TE_NO_OVERLAP",
+                                "TE_NO_FUSE3_CF", "TE_NO_CFP", "TE_NO_XF", "TE_NO_FCORR", "TE_NO_FCORR_CF", "TE_NO_OVERLAP",
                                 "TE_OVERLAP_MIN", "TE_NO_PS_FACES", "TE_PS_MODE", "TE_PS_SLOW", "TE_RBGS_NOSLAB", "TE_ZS_FORCE", "TE_NO_ZS8",
-                                "TE_RESWEEP_V", "TE_EXCHANGE_TIMEOUT", "TE_NO_VERIFY", "TE_RCCL_LOOPBACK", "TE_ZR_AHEAD", "TE_NO_BICG_FUSE", "TE_POST_EXCHANGE", "TE_REPL_BLOCKS", "TE_PACK_FACES", "TE_OVERLAP_MODE", "TE_PUSH_TIMEOUT", "TE_NO_BICG_XF", "TE_PUSH_FAULT", "TE_2D_NO_FOLD", "TE_2D_NO_SYM", "TE_PUSH_NONFATAL", "TE_PS_NO_HALF", "TE_PS_HALF_MAX", "TE_NO_GTAB2", "TE_NO_RS6_CF", "TE_NO_RS6_FIXUP", "TE_NO_CFP59", "TE_SCHUR_FULL", "TE_ZS_PIN"};
+                                "TE_RESWEEP_V", "TE_EXCHANGE_TIMEOUT", "TE_NO_VERIFY", "TE_RCCL_LOOPBACK", "TE_NO_BICG_FUSE", "TE_POST_EXCHANGE", "TE_REPL_BLOCKS", "TE_PACK_FACES", "TE_OVERLAP_MODE", "TE_PUSH_TIMEOUT", "TE_NO_BICG_XF", "TE_PUSH_FAULT", "TE_2D_NO_FOLD", "TE_2D_NO_SYM", "TE_PUSH_NONFATAL", "TE_PS_NO_HALF", "TE_PS_HALF_MAX", "TE_NO_RS6_CF", "TE_NO_RS6_FIXUP", "TE_SCHUR_FULL", "TE_ZS_PIN"};
 
 void drainEvents(te_gmg *g)
 {
@@ -42,6 +42,14 @@ static int parseSlabPin(const char *v)
 	if (!v || !v[0] || v[1]) return 0;
 	const int pin = v[0] - '0';
 	return slabPinValid(pin) ? pin : 0;
+}
+
+// the value of TE_RESWEEP_V: "19", "27" or "59" and nothing else (0: not one of them)
+static int parseResweepPin(const char *v)
+{
+	if (!v || !v[0] || !v[1] || v[2]) return 0;
+	const int pin = (v[0] - '0') * 10 + (v[1] - '0');
+	return resweepPinValid(pin) ? pin : 0;
 }
 
 // places the tables of level li (level_tables.cpp) on the device; the order of the allocations is part of the set-up's behaviour
@@ -185,6 +193,8 @@ int te_gmg_create(const te_hier *h, int device, te_gmg **out)
 		g->cfg.fromEnv();
 		if (g->cfg.has(O_ZS_PIN) && !(g->zs_pin = parseSlabPin(g->cfg.str(O_ZS_PIN)))) // (before the solver owns anything)
 			return te::fail(TE_EINVAL, "te_gmg_create: TE_ZS_PIN must be 1, 2, 4 or 8");
+		if (g->cfg.has(O_RESWEEP_V) && !(g->resweep_pin = parseResweepPin(g->cfg.str(O_RESWEEP_V))))
+			return te::fail(TE_EINVAL, "te_gmg_create: TE_RESWEEP_V must be 19, 27 or 59");
 		HIPCHK(hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking));
 		HIPCHK(hipStreamCreateWithFlags(&g->comm_stream, hipStreamNonBlocking));
 		HIPCHK(hipEventCreateWithFlags(&g->ev_pack, hipEventDisableTiming));
@@ -603,6 +613,11 @@ int te_gmg_set_option(te_gmg *g, const char *name, const char *value)
 						const int pin = parseSlabPin(value);
 						if (value && !pin) return te::fail(TE_EINVAL, "te_gmg_set_option: TE_ZS_PIN must be 1, 2, 4 or 8");
 						g->zs_pin = pin;
+					}
+					if (o == O_RESWEEP_V) {
+						const int pin = parseResweepPin(value);
+						if (value && !pin) return te::fail(TE_EINVAL, "te_gmg_set_option: TE_RESWEEP_V must be 19, 27 or 59");
+						g->resweep_pin = pin;
 					}
 					g->cfg.set(o, value);
 					if (o == O_PUSH_TIMEOUT) g->push.timeout_s = value ? std::max(0.1, atof(value)) : (g->wd.timeout_s > 0 ? g->wd.timeout_s : 300.0);

@@ -37,33 +37,19 @@ int zeroSweepResidN(te_gmg *g, LevelHost &L, const double *f, double *out, doubl
 		} else {
 			D.f6_out = L.f6buf.p;
 			D.fcorr  = fcorr_in;
-			// TE_ZR_AHEAD = 1: the right-hand side requested one plane ahead only (the form before round 3; bit-identical)
-			const bool ah1 = g->cfg.num(O_ZR_AHEAD, 4) == 1;
-#define TE_ZR(EXP, FC)                                                                                                   \
-	if (ah1)                                                                                                             \
-		launchT(t, (k_rbgs_zero_resid3d<N, false, EXP, FC, 1>), grid, blk, 0, g->stream, D, f, out, rd, FSrc());         \
-	else                                                                                                                 \
-		launchT(t, (k_rbgs_zero_resid3d<N, false, EXP, FC, 4>), grid, blk, 0, g->stream, D, f, out, rd, FSrc())
-			if (fs) { // the right-hand side is a pending vector statement of te_bicgstab (march3d.hpp FSrc): formed and stored here
-				const FSrc a = fs->args;
-				if (fs->kind == 1 && export_rs6)
-					launchT(t, (k_rbgs_zero_resid3d<N, false, true, false, 4, 1>), grid, blk, 0, g->stream, D, f, out, rd, a);
-				else if (fs->kind == 1)
-					launchT(t, (k_rbgs_zero_resid3d<N, false, false, false, 4, 1>), grid, blk, 0, g->stream, D, f, out, rd, a);
-				else if (export_rs6)
-					launchT(t, (k_rbgs_zero_resid3d<N, false, true, false, 4, 2>), grid, blk, 0, g->stream, D, f, out, rd, a);
-				else
-					launchT(t, (k_rbgs_zero_resid3d<N, false, false, false, 4, 2>), grid, blk, 0, g->stream, D, f, out, rd, a);
-			} else if (export_rs6 && fcorr_in) {
-				TE_ZR(true, true);
-			} else if (export_rs6) {
-				TE_ZR(true, false);
-			} else if (fcorr_in) {
-				TE_ZR(false, true);
-			} else {
-				TE_ZR(false, false);
-			}
-#undef TE_ZR
+			dispatchBool(export_rs6, [&](auto ex) {
+				constexpr bool EXP = decltype(ex)::value;
+				if (fs) { // the right-hand side is a pending vector statement of te_bicgstab (march3d.hpp FSrc): formed and stored here
+					// (level 0 only, whose right-hand side never carries exported terms: FS != 0 is never combined with FCORR)
+					if (fs->kind == 1)
+						launchT(t, (k_rbgs_zero_resid3d<N, false, EXP, false, 1>), grid, blk, 0, g->stream, D, f, out, rd, fs->args);
+					else
+						launchT(t, (k_rbgs_zero_resid3d<N, false, EXP, false, 2>), grid, blk, 0, g->stream, D, f, out, rd, fs->args);
+				} else
+					dispatchBool(fcorr_in != nullptr, [&](auto fc) {
+						launchT(t, (k_rbgs_zero_resid3d<N, false, EXP, decltype(fc)::value>), grid, blk, 0, g->stream, D, f, out, rd, FSrc());
+					});
+			});
 		}
 	}
 	// the new face layers of neighbours on other ranks (no-op on one rank)
@@ -71,33 +57,25 @@ int zeroSweepResidN(te_gmg *g, LevelHost &L, const double *f, double *out, doubl
 	L.ghost_has_v = !store_u; // (the slots of neighbours on other ranks hold their face layers of v until the next exchange of the level)
 	if (fcorr_out) { // the ghost terms were formed by the patches that own the face values: sort them into the coarse
 		// level's side array (a permutation copy of 6/128 of a vector instead of the fix-up pass)
-		if (L.Pc > 0 && !g->cfg.has(O_NO_GTAB2) && !g->cfg.has(O_NO_GTAB)) { // descriptors once per level, then 16-byte data loads only (k_fcorr_gather3d_v2)
-			LevelDev  D   = L.dev();
-			const int key = (export_rs6 ? 1 : 0) | (D.f6off ? 2 : 0);
-			if (L.gdesc_key != key) { // (built once; again if the face layers change their layout: TE_PACK_FACES)
+		if (L.Pc > 0) { // descriptors once per level, then 16-byte data loads only (k_fcorr_gather3d_v2)
+			LevelDev   D       = L.dev();
+			const int  key     = (export_rs6 ? 1 : 0) | (D.f6off ? 2 : 0);
+			const bool rebuild = L.gdesc_key != key; // (built once; again if the face layers change their layout: TE_PACK_FACES)
+			if (rebuild) {
 				int rc2 = L.gdesc.p ? TE_OK : L.gdesc.alloc((size_t) L.Pc * 48);
 				if (rc2) return rc2;
 				hipLaunchKernelGGL(k_gather_desc3d<N>, dim3(L.Pc), dim3(64), 0, g->stream, D, L.child.p, L.copy.p, export_rs6 ? 1 : 0, L.gdesc.p);
 				L.gdesc_key = key;
 			}
-			if (L.fcorr_zeroed_for != fcorr_out) { // (planes without a term are never stored: k_fcorr_gather3d_v2; the other gathers store every entry)
+			// the gather never stores a plane without a term: the side array's zeros are set here, for every new set of descriptors
+			// and every new side array (LevelHost::fcorr: the gather is its only writer)
+			if (rebuild || L.fcorr_zeroed_for != fcorr_out) {
 				HIPCHK(hipMemsetAsync(fcorr_out, 0, sizeof(double) * (size_t) L.Pc * 4 * N * N, g->stream));
 				L.fcorr_zeroed_for = fcorr_out;
 			}
 			Timed t(g, KC_FCORR_GATHER, (size_t) L.P * 6 * L.nf / 4);
 			hipLaunchKernelGGL(k_fcorr_gather3d_v2<N>, dim3(L.Pc * 12), dim3(256), 0, g->stream, D, (const GatherDesc *) L.gdesc.p,
 			                   export_rs6 ? (const double *) L.rs6.p : (const double *) nullptr, (const double *) L.f6buf.p, coarse, fcorr_out);
-		} else if (L.Pc > 0) {
-			const bool use_gtab = export_rs6 && !g->cfg.has(O_NO_GTAB);
-			if (use_gtab && !L.gtab.p && (size_t) L.P * 6 * (N / 2) * (N / 2) < ((size_t) 1 << 31)) { // once per level
-				int rc2 = L.gtab.alloc((size_t) L.Pc * 48);
-				if (rc2) return rc2;
-				hipLaunchKernelGGL(k_gather_table3d<N>, dim3(L.Pc), dim3(64), 0, g->stream, L.dev(), L.child.p, L.copy.p, L.gtab.p);
-			}
-			Timed t(g, KC_FCORR_GATHER, (size_t) L.P * 6 * L.nf / 4);
-			hipLaunchKernelGGL(k_fcorr_gather3d<N>, dim3(L.Pc * 12), dim3(256), 0, g->stream, L.dev(), L.child.p, L.copy.p,
-			                   export_rs6 ? (const double *) L.rs6.p : (const double *) nullptr, (const double *) L.f6buf.p, coarse, fcorr_out,
-			                   use_gtab ? (const int32_t *) L.gtab.p : (const int32_t *) nullptr);
 		}
 	} else if (L.P > 0) {
 		Timed    t(g, KC_FIXUP, (size_t) L.P * 6 * L.nf);
@@ -118,66 +96,33 @@ int zeroSweepResidN(te_gmg *g, LevelHost &L, const double *f, double *out, doubl
 template <int N>
 int resweepProlongN(te_gmg *g, LevelHost &L, const double *f, double *out, const double *prolong_from, double *xf_out, const double *fcorr_in)
 {
-	ProlongSrc ps     = prolongSrc(L, prolong_from);
-	auto       launch = [&](LevelDev D) {
+	ProlongSrc ps      = prolongSrc(L, prolong_from);
+	const bool refined = L.ncf > 0 || L.has_copy; // copy-through patches / coarse-fine ghost slots
+	// the kernel's tuning variant (dispatch.hpp resweepVariant: the defaults and what each was measured against; all bit-identical)
+	const int v = resweepVariant(fcorr_in != nullptr, refined, L.index, (size_t) L.P * L.nc * sizeof(double), g->resweep_pin);
+	if (!v) return te::fail(TE_ESTATE, "resweepProlong: exported ghost terms on a refined level");
+	auto launch = [&](LevelDev D) {
 		if (D.count == 0) return;
 		Timed t(g, fcorr_in ? KC_RESWEEP_FCORR : KC_RESWEEP, (size_t) D.count * L.nc, true);
 		D.f6    = L.f6buf.p;
 		D.fcorr = fcorr_in;
-		if constexpr (N >= 4) {
-			const dim3  grid = slabGrid(D.count), blk(Tile3<N>::TPB);
-			// tuning variants (march3d.hpp), all bit-identical. Defaults, each measured: the finest level stores u non-temporally
-			// (nobody re-reads it) and loads f non-temporally unless f can still be in the Infinity Cache from the pre-sweep
-			// that read it (19 instead of 27: 256^3, a rank's share at eight ranks; 53.4 -> 49.0 us at 256^3); a large finest
-			// level runs two workgroups per CU with four planes of f in flight each instead of three with two (59: 450 -> 443 us
-			// at 512^3, same box; slower at 256^3); a coarser level with exported ghost terms (level 1 of 512^3) keeps ordinary
-			// stores as well -- its u is the correction the finer level's post-sweep reads next (3: 64.5 us, against 68.7 with
-			// non-temporal stores)
-			const char *ve    = g->cfg.str(O_RESWEEP_V);
-			const bool  small = (size_t) L.P * L.nc * sizeof(double) <= ((size_t) 160 << 20);
-			const int   v     = ve ? atoi(ve) : (fcorr_in ? 3 : (L.index != 0 ? 27 : (small ? 19 : 59)));
-			if (L.ncf > 0 || L.has_copy) { // refined level: copy-through patches / coarse-fine ghost slots
-				if (v == 3)
-					launchT(t, (k_rbgs_resweep_prolong3d<N, 3, false, true>), grid, blk, 0, g->stream, D, f, out, ps);
-				else if (v == 59 && !g->cfg.has(O_NO_CFP59))
-					launchT(t, (k_rbgs_resweep_prolong3d<N, 59, false, true>), grid, blk, 0, g->stream, D, f, out, ps);
-				else
-					launchT(t, (k_rbgs_resweep_prolong3d<N, 27, false, true>), grid, blk, 0, g->stream, D, f, out, ps);
-			} else if (fcorr_in) {
-				if (v == 0)
-					launchT(t, (k_rbgs_resweep_prolong3d<N, 0, true>), grid, blk, 0, g->stream, D, f, out, ps);
-				else if (v == 27)
-					launchT(t, (k_rbgs_resweep_prolong3d<N, 27, true>), grid, blk, 0, g->stream, D, f, out, ps);
-				else if (v == 19)
-					launchT(t, (k_rbgs_resweep_prolong3d<N, 19, true>), grid, blk, 0, g->stream, D, f, out, ps);
-				else
-					launchT(t, (k_rbgs_resweep_prolong3d<N, 3, true>), grid, blk, 0, g->stream, D, f, out, ps);
-			} else if (v == 0) {
-				launchT(t, (k_rbgs_resweep_prolong3d<N, 0, false>), grid, blk, 0, g->stream, D, f, out, ps);
-			} else if (v == 7) {
-				launchT(t, (k_rbgs_resweep_prolong3d<N, 7, false>), grid, blk, 0, g->stream, D, f, out, ps);
-			} else if (v == 11) {
-				launchT(t, (k_rbgs_resweep_prolong3d<N, 11, false>), grid, blk, 0, g->stream, D, f, out, ps);
-			} else if (v == 19) {
-				launchT(t, (k_rbgs_resweep_prolong3d<N, 19, false>), grid, blk, 0, g->stream, D, f, out, ps);
-			} else if (v == 59) {
-				launchT(t, (k_rbgs_resweep_prolong3d<N, 59, false>), grid, blk, 0, g->stream, D, f, out, ps);
-			} else if (v == 63) {
-				launchT(t, (k_rbgs_resweep_prolong3d<N, 63, false>), grid, blk, 0, g->stream, D, f, out, ps);
-			} else if (v == 23) {
-				launchT(t, (k_rbgs_resweep_prolong3d<N, 23, false>), grid, blk, 0, g->stream, D, f, out, ps);
-			} else if (v == 31) {
-				launchT(t, (k_rbgs_resweep_prolong3d<N, 31, false>), grid, blk, 0, g->stream, D, f, out, ps);
-			} else if (v == 27) {
-				launchT(t, (k_rbgs_resweep_prolong3d<N, 27, false>), grid, blk, 0, g->stream, D, f, out, ps);
-			} else if (v == 3) {
-				launchT(t, (k_rbgs_resweep_prolong3d<N, 3, false>), grid, blk, 0, g->stream, D, f, out, ps);
-			} else {
-				launchT(t, (k_rbgs_resweep_prolong3d<N, 27, false>), grid, blk, 0, g->stream, D, f, out, ps);
-			}
+		const dim3 grid = slabGrid(D.count), blk(Tile3<N>::TPB);
+		if (refined) {
+			if (v == 59)
+				launchT(t, (k_rbgs_resweep_prolong3d<N, 59, false, true>), grid, blk, 0, g->stream, D, f, out, ps);
+			else
+				launchT(t, (k_rbgs_resweep_prolong3d<N, 27, false, true>), grid, blk, 0, g->stream, D, f, out, ps);
+		} else if (v == 3) {
+			launchT(t, (k_rbgs_resweep_prolong3d<N, 3, true>), grid, blk, 0, g->stream, D, f, out, ps);
+		} else if (v == 19) {
+			launchT(t, (k_rbgs_resweep_prolong3d<N, 19>), grid, blk, 0, g->stream, D, f, out, ps);
+		} else if (v == 59) {
+			launchT(t, (k_rbgs_resweep_prolong3d<N, 59>), grid, blk, 0, g->stream, D, f, out, ps);
+		} else {
+			launchT(t, (k_rbgs_resweep_prolong3d<N, 27>), grid, blk, 0, g->stream, D, f, out, ps);
 		}
 	};
-	if (L.post_exchange_free && L.ghost_has_v && L.ncf == 0 && !L.has_copy && !g->cfg.has(O_POST_EXCHANGE)) {
+	if (L.post_exchange_free && L.ghost_has_v && !refined && !g->cfg.has(O_POST_EXCHANGE)) {
 		// every neighbour's parent is local (the coarser level lives on every rank) and the ghost slots still hold the neighbours'
 		// face layers of v: the kernel forms v + P e for them as for local neighbours; nothing travels (a global decision: all
 		// ranks of the level take it together)

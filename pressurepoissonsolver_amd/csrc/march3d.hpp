@@ -15,12 +15,6 @@
 #include "kernels3d.hpp"
 #include <type_traits>
 
-#ifndef TE_ZR_WIDE
-#define TE_ZR_WIDE 1 // (0: tooling -- every variant of the fused pre-sweep at three workgroups per CU, as before round 6's end)
-#endif
-#ifndef TE_ZR_NT
-#define TE_ZR_NT 0 // (non-temporal loads of f in the pre-sweep cost more in the post-sweep, which finds less of f in the Infinity Cache)
-#endif
 namespace te
 {
 // streaming accesses that nothing re-reads before they leave the caches (a 1 GiB vector per pass): non-temporal
@@ -855,7 +849,7 @@ __global__ __launch_bounds__(Tile3<N>::TPB) void k_rbgs3d(LevelDev L, const doub
 // face cells) to the coarse cell behind the block. For x faces those coarse cells sit one per 64-byte sector: over a whole
 // level the fix-up reads and rewrites every sector of the coarse vector, 0.10 ms of a 1.09 ms cycle at 512^3. Instead, the
 // patch that OWNS the face values forms the finished terms (it holds the values in registers when its plane is final),
-// k_fcorr_gather3d adds the y and z terms to the coarse right-hand side in place (contiguous rows and planes) and sorts
+// k_fcorr_gather3d_v2 adds the y and z terms to the coarse right-hand side in place (contiguous rows and planes) and sorts
 // the x terms into a compact side array of the coarse level, `fcorr` [coarse patch][4][N*N]: planes x = 0, H-1, H, N-1
 // (the x faces of the eight child octants) at (y + N z), pure stores, one writer per entry; the kernels that read the
 // coarse right-hand side (k_rbgs_zero_resid3d / k_rbgs_resweep_prolong3d with FCORR) add them while loading:
@@ -868,7 +862,7 @@ template <int N> __device__ __forceinline__ int octPlane(int c) // 0, H-1, H, N-
 	return c == 0 ? 0 : (c == H - 1 ? 1 : (c == H ? 2 : (c == N - 1 ? 3 : -1)));
 }
 // what a reader of the coarse right-hand side adds to its two rows (k) of plane z: the x terms (the y and z terms were added
-// in place by k_fcorr_gather3d). fcorr: [patch][4][N*N], plane j at (y + N z).
+// in place by k_fcorr_gather3d_v2). fcorr: [patch][4][N*N], plane j at (y + N z).
 template <int N> struct FCorrSrc {
 	// N >= 8: at most one of a thread's two cells lies on an octant face (one pointer, one pair of values); N = 4: both may
 	static constexpr int NX = (N >= 8) ? 1 : 2;
@@ -918,146 +912,27 @@ template <int N> struct FCorrSrc {
 		}
 	}
 };
-// fcorr of the coarse level from the finished 2x2 sums the fine patches left in their own `rs6` [fine patch][6][H*H]
-// (k_rbgs_zero_resid3d EXPORT writes them next to its face layers: small stores into the patch's own region -- written
-// straight into six far-away coarse planes they stalled the kernel's in-order memory pipeline and doubled its time).
-// One workgroup per coarse patch and plane: entry (a, b) of plane j of axis ax belongs to child octant o; the term
-// comes from the patch across that child's face: rs6 of a local neighbour, or (neighbour on another rank) the sums of
-// k_restrict_fixup3d formed here from the ghost slot. Physical faces: +0. A pure permutation copy of finished values.
-// rs6 == null (a refined fine level: copy-through patches, coarse/fine ghost slots): the sums are formed here from the
-// fine level's face layers f6; a coarse patch that is a copy of a fine patch takes w g cell by cell on its own two faces
-// of each axis, as the copy-through branch of k_restrict_fixup3d adds them.
-// gtab [coarse patch][axis][plane j][quadrant oa + 2 ob] (built once per level by k_gather_table3d): where in rs6 the 16x16
-// block of finished terms of that quarter plane starts; -1: the terms are zero (physical face, no such child); -2: take the
-// general path (neighbour on another rank, copy-through patch). One cached table read instead of the dependent chain
-// child -> face kind / source -> value (the kernel is all latency: 90 % of its wave cycles wait). Tried and dropped: a thread's
-// four entries in stages (indices together, then values together from a harmless address where there is nothing to read, the
-// general chain only where the table has no answer): 36 -> 52-59 us on the same box.
-template <int N>
-__global__ void k_gather_table3d(LevelDev L, const int32_t *__restrict__ child, const int32_t *__restrict__ copy, int32_t *__restrict__ gtab)
-{
-	constexpr int HH = (N / 2) * (N / 2);
-	const int     pc = blockIdx.x, e = threadIdx.x;
-	if (e >= 48) return;
-	const int ax = e / 16, j = (e / 4) % 4, oa = e & 1, ob = (e >> 1) & 1;
-	int32_t   v;
-	if (copy && copy[pc]) {
-		v = -2;
-	} else {
-		const int a0 = (ax == 0) ? 1 : 0, a1 = (ax == 2) ? 1 : 2;
-		const int s = 2 * ax + (j & 1), hi = j >> 1;
-		const int p = child[(size_t) pc * 8 + ((hi << ax) | (oa << a0) | (ob << a1))];
-		if (p < 0) {
-			v = -1;
-		} else {
-			const int kind = L.face_kind[(size_t) p * 6 + s], src = L.face_src[(size_t) p * 6 + s];
-			v              = kind < FACE_LOCAL ? -1 : (kind == FACE_LOCAL ? (int32_t) (((size_t) src * 6 + (s ^ 1)) * HH) : -2);
-		}
-	}
-	gtab[(size_t) pc * 48 + e] = v;
-}
-template <int N>
-__global__ __launch_bounds__(256) void k_fcorr_gather3d(LevelDev L, const int32_t *__restrict__ child, const int32_t *__restrict__ copy,
-                                                        const double *__restrict__ rs6, const double *__restrict__ f6,
-                                                        double *__restrict__ coarse, double *__restrict__ fcorr,
-                                                        const int32_t *__restrict__ gtab)
-{
-	constexpr int NN = N * N, NNN = N * N * N, H = N / 2, HH = H * H;
-	// one workgroup per plane; a thread's QN entries are independent chains of dependent loads (tables, then the value): all
-	// terms first, then the stores, so that the chains overlap
-	constexpr int QN = (NN + 255) / 256;
-	const int     pc = blockIdx.x / 12, blk = blockIdx.x % 12; // 0..3: the x planes; 4..7: the y planes; 8..11: the z planes
-	const bool    cp = copy && copy[pc];
-	// the term of entry (a, b) of plane j of axis ax of this coarse patch
-	auto term = [&](int ax, int j, int a, int b) -> double {
-		if (rs6 && gtab) { // (a uniformly refined fine level: the finished sums of the neighbours)
-			const int oa = a >= H, ob = b >= H;
-			const int t  = gtab[(size_t) pc * 48 + ax * 16 + j * 4 + oa + 2 * ob];
-			if (t >= 0) return rs6[(size_t) t + (a - oa * H) + H * (b - ob * H)];
-			if (t == -1) return 0.0;
-		}
-		const int a0 = (ax == 0) ? 1 : 0, a1 = (ax == 2) ? 1 : 2; // the two other axes in order
-		if (cp) { // the coarse patch IS a fine patch that does not coarsen: its own two faces of the axis, cell by cell (w g)
-			if (j == 1 || j == 2) return 0.0;
-			const int p = child[(size_t) pc * 8], sp = 2 * ax + (j == 3);
-			if (p < 0) return 0.0;
-			const int kind = L.face_kind[(size_t) p * 6 + sp], src = L.face_src[(size_t) p * 6 + sp];
-			if (kind < FACE_LOCAL) return 0.0;
-			const double g = kind == FACE_GHOST ? L.ghost[(size_t) src * NN + a + N * b] : f6[f6Face<N>(L.f6off, src, sp ^ 1) + a + N * b];
-			return -L.rh2[(size_t) p * 3 + ax] * g;
-		}
-		const int s = 2 * ax + (j & 1), hi = j >> 1; // j = 0: low face of the low child, 1: its high face, 2, 3: the high child's
-		const int oa = a >= H, ob = b >= H, ha = a - oa * H, hb = b - ob * H;
-		const int p = child[(size_t) pc * 8 + ((hi << ax) | (oa << a0) | (ob << a1))];
-		if (p < 0) return 0.0;
-		const int kind = L.face_kind[(size_t) p * 6 + s], src = L.face_src[(size_t) p * 6 + s];
-		if (kind < FACE_LOCAL) return 0.0;
-		if (kind == FACE_LOCAL && rs6) return rs6[((size_t) src * 6 + (s ^ 1)) * HH + ha + H * hb];
-		// the sum of k_restrict_fixup3d over the 2x2 block, first face coordinate fastest
-		const double  w  = -L.rh2[(size_t) p * 3 + ax];
-		const double *gp = kind == FACE_GHOST ? L.ghost + (size_t) src * NN : f6 + f6Face<N>(L.f6off, src, s ^ 1);
-		double        v  = 0.0;
-#pragma unroll
-		for (int db = 0; db < 2; db++)
-#pragma unroll
-			for (int da = 0; da < 2; da++) v += (w * gp[(2 * ha + da) + N * (2 * hb + db)]) / 8;
-		return v;
-	};
-	constexpr int coord[4] = {0, H - 1, H, N - 1};
-	double       *cv       = coarse + (size_t) pc * NNN;
-	const int     j        = blk & 3;
-	double        v[QN], vy[QN], f[QN];
-	if (blk < 4) { // an x plane: into the side array
-#pragma unroll
-		for (int k = 0; k < QN; k++) {
-			const int i = threadIdx.x + 256 * k;
-			v[k]        = i < NN ? term(0, j, i % N, i / N) : 0.0;
-		}
-#pragma unroll
-		for (int k = 0; k < QN; k++) {
-			const int i = threadIdx.x + 256 * k;
-			if (i < NN) fcorr[((size_t) pc * 4 + j) * NN + i] = v[k];
-		}
-	} else if (blk < 8) { // a y plane: entry (x, z) -> cell (x, coord[j], z); the cells that also lie on a z plane are that plane's
-#pragma unroll
-		for (int k = 0; k < QN; k++) {
-			const int i = threadIdx.x + 256 * k, a = i % N, b = i / N;
-			v[k]        = (i < NN && octPlane<N>(b) < 0) ? term(1, j, a, b) : 0.0;
-		}
-#pragma unroll
-		for (int k = 0; k < QN; k++) {
-			const int i = threadIdx.x + 256 * k, a = i % N, b = i / N;
-			if (v[k] != 0.0) cv[a + N * coord[j] + NN * b] += v[k];
-		}
-	} else { // a z plane: entry (x, y) -> cell (x, y, coord[j]); a cell that lies on a y plane too takes its y term first
-#pragma clang fp contract(off)
-#pragma unroll
-		for (int k = 0; k < QN; k++) {
-			const int i = threadIdx.x + 256 * k, a = i % N, b = i / N, jy = octPlane<N>(b);
-			const bool in = i < NN;
-			f[k]          = in ? cv[a + N * b + NN * coord[j]] : 0.0;
-			vy[k]         = (in && jy >= 0) ? term(1, jy, a, coord[j]) : 0.0;
-			v[k]          = in ? term(2, j, a, b) : 0.0;
-		}
-#pragma unroll
-		for (int k = 0; k < QN; k++) {
-			const int i = threadIdx.x + 256 * k, a = i % N, b = i / N;
-			double    t = f[k];
-			if (vy[k] != 0.0) t = t + vy[k];
-			if (v[k] != 0.0) t = t + v[k];
-			if (vy[k] != 0.0 || v[k] != 0.0) cv[a + N * b + NN * coord[j]] = t;
-		}
-	}
-}
-
-// k_fcorr_gather3d, round 6. The kernel above walks child -> face kind / source -> f6 offset -> values for EVERY entry in EVERY thread:
-// on a refined fine level (no rs6, no table) each entry costs five dependent loads and ~9 load instructions of which 4 fetch data --
-// 150 us per launch at 0.97 TB/s on `2refine --divide 3` (profiles/r05_bench_c4_2refine_div3_n1.json) -- and on a uniform one a table
-// word per entry. But the walk depends on the (coarse patch, axis, plane, quadrant) only: 48 answers per coarse patch. k_gather_desc3d
-// writes them down once per level as descriptors -- what to read (finished sums of a neighbour / a 2x2 sum over a face layer or a
-// ghost slot / a copy-through patch's own face, cell by cell), where, and the weight -- and the gather keeps the (at most 12)
-// descriptors of its plane in LDS: a thread issues nothing but 16-byte data loads, two adjacent entries at a time. The values,
-// the order of the additions and the stores are those of k_fcorr_gather3d (bit-identical; TE_NO_GTAB runs the kernel above).
+// fcorr of the coarse level, and the y and z terms of its right-hand side, from what the fine level's pre-sweep left behind.
+// A TERM is what k_restrict_fixup3d would add to one coarse cell behind one fine face: the sum over the 2x2 block of face cells of
+// (w g) / 8, first face coordinate fastest, w = -1/h^2 of the axis, g = the neighbour's value behind the face. Entry (a, b) of
+// octant plane j (x = 0, H-1, H, N-1; likewise y, z) of axis ax of a coarse patch belongs to the child octant that holds it --
+// j = 0: the low face of the low child, 1: its high face, 2, 3: the high child's -- and its term comes from the patch across that
+// child's face:
+//   * a local neighbour whose pre-sweep exported its finished sums (k_rbgs_zero_resid3d EXPORT -> `rs6` [fine patch][6][H*H]):
+//     the sum itself, a pure permutation copy. The sums go to the patch's own rs6, next to its face layers, and NOT straight into
+//     the six coarse planes they end up in: small stores into far-away planes stalled the pre-sweep's in-order memory pipeline
+//     and doubled its time;
+//   * a local neighbour without rs6 (a refined fine level: copy-through patches, coarse/fine ghost slots), or a neighbour on
+//     another rank: the sum formed here from the fine level's face layers f6 / from the ghost slot;
+//   * a coarse patch that IS a fine patch that does not coarsen: w g cell by cell on its own two faces of each axis, as the
+//     copy-through branch of k_restrict_fixup3d adds them;
+//   * a physical face, or no such child: nothing (+0 in fcorr).
+// Which of these, where, and the weight depends on (coarse patch, axis, plane, quadrant) only: 48 answers per coarse patch, not one
+// per entry. k_gather_desc3d walks child -> face kind / source -> offset once per level and writes the answers down as
+// descriptors (walked per entry, a refined fine level cost five dependent loads and ~9 load instructions an entry of which 4
+// fetched data: 150 us per launch at 0.97 TB/s on `2refine --divide 3`, profiles/r05_bench_c4_2refine_div3_n1.json);
+// k_fcorr_gather3d_v2 keeps the (at most 12) descriptors of its plane in LDS and issues nothing but 16-byte data loads, two
+// adjacent entries at a time.
 struct GatherDesc {
 	int32_t mode, pad;
 	int64_t off; // doubles, inside rs6 / f6 / the ghost planes
@@ -1126,6 +1001,14 @@ __device__ __forceinline__ double2 gatherPair(const GatherDesc &d, int a, int b,
 	v.y += (d.w * r10.x) / 8, v.y += (d.w * r10.y) / 8, v.y += (d.w * r11.x) / 8, v.y += (d.w * r11.y) / 8;
 	return v;
 }
+// One workgroup per coarse patch and octant plane (12 of them). An x plane goes to the side array `fcorr`, pure stores, one writer
+// per entry. A y plane's terms are added to the coarse right-hand side in place, except on the rows that lie on a z plane too:
+// those belong to the z plane's workgroup, which adds the y term first and the z term second (f = (f + y term) + z term, the
+// order in which k_restrict_fixup3d visits the faces; a term that is 0 is not added, so -0 stays -0). All of a thread's loads
+// first, then its stores, so that the loads overlap.
+// Invariant of `fcorr`: this kernel is its ONLY writer, and a plane none of whose descriptors has a term is never stored. Its
+// zeros are those of the hipMemsetAsync that zeroSweepResidN issues whenever it builds the descriptors or meets another side
+// array; with the same descriptors the same entries are written on every launch.
 template <int N>
 __global__ __launch_bounds__(256) void k_fcorr_gather3d_v2(LevelDev L, const GatherDesc *__restrict__ gd, const double *__restrict__ rs6,
                                                            const double *__restrict__ f6, double *__restrict__ coarse, double *__restrict__ fcorr)
@@ -1224,8 +1107,10 @@ __global__ __launch_bounds__(256) void k_fcorr_gather3d_v2(LevelDev L, const Gat
 // EXPORT: the ghost terms of the restricted residual that this patch's face values contribute to its neighbours' coarse
 // cells go to rd.fcorr (see above) -- no k_restrict_fixup3d pass; FCORR: this level's own right-hand side carries such
 // terms in L.fcorr (it was produced that way by the finer level).
-// AH: how many planes ahead of the red update the right-hand side is requested (1: the plane of the next step only -- then
-// every step waits for a load issued one step earlier, and a step is shorter than an HBM miss under load; 3: the default).
+// The right-hand side is requested AH = 4 planes ahead of the red update (one plane ahead, every step waits for a load issued
+// one step earlier, and a step is shorter than an HBM miss under load), with ordinary loads: non-temporal ones here cost more in
+// the post-sweep, which then finds less of f in the Infinity Cache. The variants that export and also read ghost terms or form
+// p (FS = 2) run two workgroups per CU, the others three.
 // FS (te_bicgstab, level 0): the right-hand side of the cycle is itself a vector statement of the Krylov loop that nobody has
 // executed yet -- FS = 1: s = resid + ap * (-alpha) (BiCGStab.h:79-80); FS = 2: p = beta (p + ap * (-omega)) + resid (:99-100).
 // This kernel, the first reader, forms it from its operands (the expressions of k_bicg_s / k_bicg_p, explicit FMAs in both
@@ -1244,11 +1129,11 @@ template <int FS> __device__ __forceinline__ double2 fsrcCombine(const FSrc &fs,
 	const double tx = __builtin_fma(b.x, fs.s1, a.x), ty = __builtin_fma(b.y, fs.s1, a.y);
 	return double2{__builtin_fma(fs.s2, tx, c.x), __builtin_fma(fs.s2, ty, c.y)};
 }
-template <int N, bool STORE_U, bool EXPORT = false, bool FCORR = false, int AH = 4, int FS = 0>
-__global__ __launch_bounds__(Tile3<N>::TPB, (TE_ZR_WIDE && EXPORT && (FS == 2 || FCORR)) ? 2 : 3) void k_rbgs_zero_resid3d(LevelDev L, const double *__restrict__ f,
+template <int N, bool STORE_U, bool EXPORT = false, bool FCORR = false, int FS = 0>
+__global__ __launch_bounds__(Tile3<N>::TPB, (EXPORT && (FS == 2 || FCORR)) ? 2 : 3) void k_rbgs_zero_resid3d(LevelDev L, const double *__restrict__ f,
                                                                      double *__restrict__ out, RestrictDst rd, FSrc fs = FSrc())
 {
-	static_assert(FS == 0 || (!FCORR && !STORE_U && AH >= 2), "the fused right-hand sides exist for the level-0 path of te_bicgstab");
+	static_assert(FS == 0 || (!FCORR && !STORE_U), "the fused right-hand sides exist for the level-0 path of te_bicgstab");
 	using T           = Tile3<N>;
 	constexpr int TPB = T::TPB, NP = T::NP, H = T::H;
 	constexpr int NN  = N * N, NNN = N * N * N;
@@ -1322,7 +1207,7 @@ __global__ __launch_bounds__(Tile3<N>::TPB, (TE_ZR_WIDE && EXPORT && (FS == 2 ||
 	double racc = 0.0;
 
 	// new iterate: u3 = plane z-3, u2 = z-2, u1 = z-1, u0 = z (all start from zero); right-hand sides alongside
-	static_assert(AH == 1 || AH == 2 || AH == 4, "planes of f in flight: the loop is unrolled over the ring's slots");
+	constexpr int AH = 4; // planes of f in flight: the loop is unrolled over the ring's slots
 	double2 u3[2], u2[2], u1[2], u0[2], f2[2], f1[2], f0[2];
 	// planes z .. z+AH-1 at the start of step z, plane p in slot p % AH. A slot is read (into f0) by the step that consumes its
 	// plane and re-requested by the same step; NO register of a plane in flight is ever copied: a ring that rotates through
@@ -1370,7 +1255,7 @@ __global__ __launch_bounds__(Tile3<N>::TPB, (TE_ZR_WIDE && EXPORT && (FS == 2 ||
 		for (int a = 0; a < AH; a++) { // planes 0 .. AH-1 (step z requests plane z+AH)
 			const int za = (a < N) ? a : N - 1;
 #pragma unroll
-			for (int k = 0; k < 2; k++) fa[a][k] = ldStream<TE_ZR_NT != 0>(fp2 + za * NP + q[k]);
+			for (int k = 0; k < 2; k++) fa[a][k] = ldStream<false>(fp2 + za * NP + q[k]);
 			if (FCORR) fc.load(za, cca[a]);
 			// in THIS order: the waits of the loop are derived from the oldest state that reaches its head, and a scheduler that
 			// issues slot 0 last here makes every iteration wait for all but the last loads
@@ -1395,7 +1280,7 @@ __global__ __launch_bounds__(Tile3<N>::TPB, (TE_ZR_WIDE && EXPORT && (FS == 2 ||
 			rawLoad(zc);
 		} else { // ... and its slot is requested again
 #pragma unroll
-			for (int k = 0; k < 2; k++) fa[SLOT][k] = ldStream<TE_ZR_NT != 0>(fp2 + zc * NP + q[k]);
+			for (int k = 0; k < 2; k++) fa[SLOT][k] = ldStream<false>(fp2 + zc * NP + q[k]);
 		}
 		if (FCORR) fc.load(zc, cca[SLOT]);
 		double *tz = tile[bz];            // plane z
@@ -1518,21 +1403,18 @@ __global__ __launch_bounds__(Tile3<N>::TPB, (TE_ZR_WIDE && EXPORT && (FS == 2 ||
 	};
 	using S0 = std::integral_constant<int, 0>;
 	using S1 = std::integral_constant<int, 1>;
-	using A1 = std::integral_constant<int, 1 % AH>;
-	using A2 = std::integral_constant<int, 2 % AH>;
-	using A3 = std::integral_constant<int, 3 % AH>;
-	static_assert(N % 4 == 0, "the march is unrolled over up to four ring slots");
+	using S2 = std::integral_constant<int, 2>;
+	using S3 = std::integral_constant<int, 3>;
+	static_assert(N % AH == 0, "the march is unrolled over the four ring slots");
 #pragma unroll 1
-	for (int z = 0; z < N; z += (AH == 4 ? 4 : 2)) {
+	for (int z = 0; z < N; z += AH) {
 		step(S0{}, S0{}, z);
-		step(S1{}, A1{}, z + 1);
-		if constexpr (AH == 4) {
-			step(S0{}, A2{}, z + 2);
-			step(S1{}, A3{}, z + 3);
-		}
+		step(S1{}, S1{}, z + 1);
+		step(S0{}, S2{}, z + 2);
+		step(S1{}, S3{}, z + 3);
 	}
 	step(S0{}, S0{}, N);     // black of plane N-1, residual of plane N-2
-	step(S1{}, A1{}, N + 1); // residual of plane N-1
+	step(S1{}, S1{}, N + 1); // residual of plane N-1
 }
 
 // Second half of the fusion above: the ghost terms of the residual along patch faces with a neighbour. One
@@ -1679,20 +1561,21 @@ __global__ void k_pack_faces6_3d(const int32_t *__restrict__ faces, const double
 	packPushTail(pp);
 }
 
-// V (tuning variants, all bit-identical): bit 0: the black values of the recomputed plane and of the sweep's plane z-1 are
-// not written back to LDS (nobody reads them: their x/y neighbours are red); bit 1: the top neighbour's plane is loaded on
-// the last steps only; bit 2: three ring slots for the planes of f in flight instead of two (a request is two steps ahead
-// of its first use instead of one; costs 8 registers: spills at three workgroups per CU); bit 3 / bit 4: non-temporal loads
-// of f / stores of u (a level's vectors are not re-read before they have left the caches: +1.4 % at 512^3, +10 % at 256^3);
-// bit 5: two workgroups per CU (256 registers) with four ring slots (with bit 2: three). Defaults: see resweepProlongN.
+// In every variant the black values of the recomputed plane and of the sweep's plane z-1 are not written back to LDS (nobody
+// reads them: their x/y neighbours are red), and the top neighbour's plane is loaded on the last steps only.
+// V (tuning variants, all bit-identical; 3, 19, 27 or 59 -- dispatch.hpp resweepVariant chooses; bits 0 and 1 are set in all
+// of them and mean nothing any more, bit 2 in none): bit 3 / bit 4: non-temporal loads of f / stores of u (a level's vectors
+// are not re-read before they have left the caches: +1.4 % at 512^3, +10 % at 256^3); bit 5: two workgroups per CU (256
+// registers) with four ring slots for the planes of f in flight instead of three workgroups with two slots.
 // FCORR: this level's right-hand side carries ghost terms in L.fcorr (see FCorrSrc)
 // CFP: a refined level, as k_rbgs3d<..., CFP>: patches that copy through take their correction cell by cell from the
 // same-size coarse patch, coarse/fine ghost slots hold u + P e already (k_cf_ghost6_3d<N, true>)
-template <int N, int V = 0, bool FCORR = false, bool CFP = false>
+template <int N, int V, bool FCORR = false, bool CFP = false>
 __global__ __launch_bounds__(Tile3<N>::TPB, (V & 32) ? 2 : 3) void k_rbgs_resweep_prolong3d(LevelDev L, const double *__restrict__ f,
                                                                           double *__restrict__ out, ProlongSrc ps)
 {
-	constexpr bool LDS_ALL = !(V & 1), TG_ALWAYS = !(V & 2), DEEP = (V & 4) != 0, NTL = (V & 8) != 0, NTS = (V & 16) != 0;
+	static_assert(V == 3 || V == 19 || V == 27 || V == 59, "the variants a default reaches");
+	constexpr bool NTL = (V & 8) != 0, NTS = (V & 16) != 0;
 	using T           = Tile3<N>;
 	constexpr int TPB = T::TPB, NP = T::NP, H = T::H;
 	constexpr int NN  = N * N, NNN = N * N * N;
@@ -1830,8 +1713,8 @@ __global__ __launch_bounds__(Tile3<N>::TPB, (V & 32) ? 2 : 3) void k_rbgs_reswee
 	auto fillBlack = [&](auto zpar, int z, double *tv, double2(&cen)[2], const double2(&below)[2], const double2(&above)[2],
 	                     const double2(&rhs)[2]) {
 		constexpr int ZP = decltype(zpar)::value;
-		relaxCell<N, 0, (1 + 0 + ZP) & 1, false, LDS_ALL>(tv, idiag, cz9of(z), lds, ldo, dix, act, rhx, rhy, rhz, cen, below, above, rhs);
-		relaxCell<N, 1, (1 + 1 + ZP) & 1, false, LDS_ALL>(tv, idiag, cz9of(z), lds, ldo, dix, act, rhx, rhy, rhz, cen, below, above, rhs);
+		relaxCell<N, 0, (1 + 0 + ZP) & 1, false, false>(tv, idiag, cz9of(z), lds, ldo, dix, act, rhx, rhy, rhz, cen, below, above, rhs);
+		relaxCell<N, 1, (1 + 1 + ZP) & 1, false, false>(tv, idiag, cz9of(z), lds, ldo, dix, act, rhx, rhy, rhz, cen, below, above, rhs);
 	};
 	using P0 = std::integral_constant<int, 0>;
 	using P1 = std::integral_constant<int, 1>;
@@ -1842,7 +1725,7 @@ __global__ __launch_bounds__(Tile3<N>::TPB, (V & 32) ? 2 : 3) void k_rbgs_reswee
 	// RING - 1 steps between a request and its first use, and no register of a plane in flight is moved.
 	// Recomputed planes r1 = v(z+1) (red entries are what is read), r2 = red(z+2) -> v(z+2), r3 = red(z+3); the sweep's planes
 	// as in k_rbgs3d
-	constexpr int RING = (V & 32) ? (DEEP ? 3 : 4) : (DEEP ? 3 : 2);
+	constexpr int RING = (V & 32) ? 4 : 2;
 	double2 fm[2], f0[2], f1[2], f2[2], fr[RING][2], r1[2], r2[2], r3[2];
 	double2 umm[2], um[2], uc[2], un[2], un2[2];
 	FCorrSrc<N> fc;
@@ -1913,14 +1796,12 @@ __global__ __launch_bounds__(Tile3<N>::TPB, (V & 32) ? 2 : 3) void k_rbgs_reswee
 	double hA = hs.p[0], hB = chalo[0];
 	double cnx = CFP ? 0.0 : cown[NN * 1 + cq], ccur = 0.0; // N >= 4: planes 2 and 3 share coarse plane 1
 	// CFP: the correction of the own patch's plane p, rows k = 0, 1, WITHOUT a branch in the march (a load under a condition makes
-	// the compiler wait for every request in flight where the branch rejoins -- on every step) and one step ahead of its use, like
-	// the halo operands: one 16-byte load per row from (base, plane stride, offset) chosen once per patch -- a patch that copies
+	// the compiler wait for every request in flight where the branch rejoins -- on every step), requested first in a step and used
+	// behind the step's barrier: one 16-byte load per row from (base, plane stride, offset) chosen once per patch -- a patch that copies
 	// through reads its two cells of the same-size coarse patch; an octant child the aligned pair that holds its coarse cell and
 	// takes the half it needs (two 32-bit selects per value: not fp64 work).
-#ifndef TE_CFP_AHEAD
-#define TE_CFP_AHEAD 0 // 1: the pairs are requested a whole step ahead (8 more registers across the step: spills at 168)
-#endif
-	const double *cfb  = cpo ? yown : cown;
+	// (Requested a whole step ahead, like the halo operands, the pairs hold 8 more registers across the step: spills at 168.)
+	const double *cfb = cpo ? yown : cown;
 	const int     cfo0 = cpo ? (2 * Yp + 0) * N + 2 * X : (cq & ~1), cfd = cpo ? N : 0; // (row 1: cfo0 + cfd)
 	const bool    cfy  = !cpo && (cq & 1);
 	auto cfLoad = [&](int p, double2(&dst)[2]) { // (p clamped by the caller)
@@ -1929,8 +1810,7 @@ __global__ __launch_bounds__(Tile3<N>::TPB, (V & 32) ? 2 : 3) void k_rbgs_reswee
 		dst[1]          = *reinterpret_cast<const double2 *>(b + cfd);
 	};
 	auto cfPick = [&](const double2 &d) { return cpo ? d : (cfy ? double2{d.y, d.y} : double2{d.x, d.x}); };
-	double2 cfn[2]; // the raw pairs of the plane the NEXT step adds its correction to
-	if (CFP && TE_CFP_AHEAD) cfLoad(2, cfn);
+	double2 cfn[2]; // the raw pairs of plane z+2, requested at the top of step z and used behind its barrier
 
 	int bz = 0; // z % 3
 	// LAST: the three steps z = N-2, N-1, N, whose plane z+2 is the top neighbour's: code of their own, so that the loads they
@@ -1953,15 +1833,8 @@ __global__ __launch_bounds__(Tile3<N>::TPB, (V & 32) ? 2 : 3) void k_rbgs_reswee
 			ccur = takeReg(cnx);
 			cnx  = (z + 4 < N) ? cown[NN * ((z + 4) >> 1) + cq] : ctop[cq];
 		}
-		if constexpr (CFP && !LAST) {
-			if constexpr (TE_CFP_AHEAD) { // plane z+2's correction arrived a step ago; plane z+3's is requested now
-#pragma unroll
-				for (int k = 0; k < 2; k++) c2v[k] = cfPick(takeRegs(cfn[k]));
-				cfLoad(z + 3 < N ? z + 3 : N - 1, cfn);
-			} else { // requested FIRST in this step, used behind its barrier: the wait leaves the ring's refill (below) in flight
-				cfLoad(z + 2, cfn);
-			}
-		}
+		// requested FIRST in this step, used behind its barrier: the wait leaves the ring's refill (below) in flight
+		if constexpr (CFP && !LAST) cfLoad(z + 2, cfn);
 		__builtin_amdgcn_sched_barrier(0);
 		// the right-hand sides move down one plane; plane z+2 leaves the ring and its slot is requested again
 #pragma unroll
@@ -1985,7 +1858,7 @@ __global__ __launch_bounds__(Tile3<N>::TPB, (V & 32) ? 2 : 3) void k_rbgs_reswee
 			}
 		}
 		double2      tg[2];
-		if constexpr (TG_ALWAYS || LAST) { // the top neighbour's plane (used on the last steps only)
+		if constexpr (LAST) { // the top neighbour's plane
 #pragma unroll
 			for (int k = 0; k < 2; k++) tg[k] = top.p[q[k]];
 		}
@@ -2011,7 +1884,7 @@ __global__ __launch_bounds__(Tile3<N>::TPB, (V & 32) ? 2 : 3) void k_rbgs_reswee
 			fillBlack(zpar, z + 2, tvz, r2, r1, r3, f2);
 #pragma unroll
 			for (int k = 0; k < 2; k++) {
-				if constexpr (CFP && !TE_CFP_AHEAD) c2v[k] = cfPick(cfn[k]);
+				if constexpr (CFP) c2v[k] = cfPick(cfn[k]);
 				un2[k] = CFP ? double2{r2[k].x + c2v[k].x, r2[k].y + c2v[k].y} : double2{r2[k].x + c2, r2[k].y + c2};
 			}
 		} else {
@@ -2028,8 +1901,8 @@ __global__ __launch_bounds__(Tile3<N>::TPB, (V & 32) ? 2 : 3) void k_rbgs_reswee
 		}
 		if (z > 0) {
 			const int cz9 = cz9of(z - 1);
-			relaxCell<N, 0, (1 + 0 + 1 - ZPAR) & 1, false, LDS_ALL>(tm, idiag, cz9, lds, ldo, dix, act, rhx, rhy, rhz, um, umm, uc, fm);
-			relaxCell<N, 1, (1 + 1 + 1 - ZPAR) & 1, false, LDS_ALL>(tm, idiag, cz9, lds, ldo, dix, act, rhx, rhy, rhz, um, umm, uc, fm);
+			relaxCell<N, 0, (1 + 0 + 1 - ZPAR) & 1, false, false>(tm, idiag, cz9, lds, ldo, dix, act, rhx, rhy, rhz, um, umm, uc, fm);
+			relaxCell<N, 1, (1 + 1 + 1 - ZPAR) & 1, false, false>(tm, idiag, cz9, lds, ldo, dix, act, rhx, rhy, rhz, um, umm, uc, fm);
 			if (act) {
 				stStream<NTS>(op2 + (z - 1) * NP + q[0], um[0]);
 				stStream<NTS>(op2 + (z - 1) * NP + q[1], um[1]);
@@ -2051,9 +1924,9 @@ __global__ __launch_bounds__(Tile3<N>::TPB, (V & 32) ? 2 : 3) void k_rbgs_reswee
 		}
 		bz = (bz == 2) ? 0 : bz + 1;
 	};
-	// unrolled over parity and ring slots: U = lcm(2, RING) steps per iteration over z < N-2, then the (N-2) % U steps left, then
-	// the three LAST steps
-	constexpr int U = (RING == 3) ? 6 : (RING == 4 ? 4 : 2);
+	// unrolled over parity and ring slots: U = RING (even) steps per iteration over z < N-2, then the (N-2) % U steps left (none,
+	// or two with four slots), then the three LAST steps
+	constexpr int U = RING;
 	using NotLast = std::integral_constant<bool, false>;
 	using Last    = std::integral_constant<bool, true>;
 	auto run = [&](auto ic, int z) {
@@ -2068,21 +1941,17 @@ __global__ __launch_bounds__(Tile3<N>::TPB, (V & 32) ? 2 : 3) void k_rbgs_reswee
 	for (; z + U <= N - 2; z += U) {
 		run(std::integral_constant<int, 0>{}, z);
 		run(std::integral_constant<int, 1>{}, z + 1);
-		if constexpr (U >= 4) {
+		if constexpr (U == 4) {
 			run(std::integral_constant<int, 2>{}, z + 2);
 			run(std::integral_constant<int, 3>{}, z + 3);
 		}
-		if constexpr (U == 6) {
-			run(std::integral_constant<int, 4>{}, z + 4);
-			run(std::integral_constant<int, 5>{}, z + 5);
-		}
 	}
 	constexpr int REM = (N - 2) % U; // (z is a multiple of U here)
-	if constexpr (REM > 0) run(std::integral_constant<int, 0>{}, z);
-	if constexpr (REM > 1) run(std::integral_constant<int, 1>{}, z + 1);
-	if constexpr (REM > 2) run(std::integral_constant<int, 2>{}, z + 2);
-	if constexpr (REM > 3) run(std::integral_constant<int, 3>{}, z + 3);
-	if constexpr (REM > 4) run(std::integral_constant<int, 4>{}, z + 4);
+	static_assert(REM == 0 || REM == 2, "N is a multiple of four");
+	if constexpr (REM == 2) {
+		run(std::integral_constant<int, 0>{}, z);
+		run(std::integral_constant<int, 1>{}, z + 1);
+	}
 	step(std::integral_constant<int, 0>{}, std::integral_constant<int, (N - 2) % RING>{}, Last{}, N - 2);
 	step(std::integral_constant<int, 1>{}, std::integral_constant<int, (N - 1) % RING>{}, Last{}, N - 1);
 	step(std::integral_constant<int, 0>{}, std::integral_constant<int, N % RING>{}, Last{}, N);

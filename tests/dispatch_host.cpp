@@ -2,7 +2,8 @@
 // a run-time patch size, dispatchSlabs<N> a run-time slab count, to the integral constant the launch sites instantiate with;
 // stencilSlabCount / rbgsSlabCount choose that count -- for every patch size, 1 ... 5000 patches, every combination of
 // TE_ZS_FORCE / TE_RBGS_NOSLAB / TE_NO_ZS8 and every TE_ZS_PIN they return a count dispatchSlabs<N> runs (never one it drops),
-// the written-out table without a pin, min(pin, largest admitted) with one.
+// the written-out table without a pin, min(pin, largest admitted) with one. resweepVariant chooses the post-sweep's kernel variant:
+// a table of every default cell and every TE_RESWEEP_V.
 #include "dispatch.hpp"
 #include <cstdio>
 #include <initializer_list>
@@ -103,6 +104,52 @@ template <int N> void checkRules()
 	for (int pin = -2; pin <= 20; pin++)
 		check(tei::slabPinValid(pin) == (pin == 1 || pin == 2 || pin == 4 || pin == 8), "slabPinValid", N, pin);
 }
+
+// The post-sweep's variant, written out cell by cell. A level: exported terms?, refined?, index, bytes; then what it runs
+// without a pin and with TE_RESWEEP_V = 19, 27, 59. 0: no kernel (exported terms never meet a refined level).
+void checkResweep()
+{
+	constexpr size_t MiB = (size_t) 1 << 20;
+	struct Row {
+		bool   exported, refined;
+		int    index;
+		size_t bytes;
+		int    dflt, pin19, pin27, pin59;
+	};
+	const Row rows[] = {
+	    // plain levels: the finest up to 160 MiB, above it, a coarser one of either size
+	    {false, false, 0, 128 * MiB, 19, 19, 27, 59},
+	    {false, false, 0, 160 * MiB, 19, 19, 27, 59},
+	    {false, false, 0, 160 * MiB + 8, 59, 19, 27, 59},
+	    {false, false, 0, 1024 * MiB, 59, 19, 27, 59},
+	    {false, false, 1, 16 * MiB, 27, 19, 27, 59},
+	    {false, false, 2, 1024 * MiB, 27, 19, 27, 59},
+	    // refined levels: 59 where a plain level runs it, 27 otherwise -- also where the pin says 19
+	    {false, true, 0, 1024 * MiB, 59, 27, 27, 59},
+	    {false, true, 0, 128 * MiB, 27, 27, 27, 59},
+	    {false, true, 1, 1024 * MiB, 27, 27, 27, 59},
+	    // exported terms: 3 whatever the level and the pin
+	    {true, false, 1, 128 * MiB, 3, 3, 3, 3},
+	    {true, false, 1, 1024 * MiB, 3, 3, 3, 3},
+	    {true, false, 0, 1024 * MiB, 3, 3, 3, 3},
+	    {true, true, 1, 128 * MiB, 0, 0, 0, 0},
+	};
+	int i = 0;
+	for (const Row &r : rows) {
+		check(tei::resweepVariant(r.exported, r.refined, r.index, r.bytes, 0) == r.dflt, "resweepVariant: the default", i, r.dflt);
+		check(tei::resweepVariant(r.exported, r.refined, r.index, r.bytes, 19) == r.pin19, "resweepVariant: pin 19", i, r.pin19);
+		check(tei::resweepVariant(r.exported, r.refined, r.index, r.bytes, 27) == r.pin27, "resweepVariant: pin 27", i, r.pin27);
+		check(tei::resweepVariant(r.exported, r.refined, r.index, r.bytes, 59) == r.pin59, "resweepVariant: pin 59", i, r.pin59);
+		i++;
+	}
+	for (int pin = -2; pin <= 70; pin++) check(tei::resweepPinValid(pin) == (pin == 19 || pin == 27 || pin == 59), "resweepPinValid", 0, pin);
+	{ // dispatchBool: the flag itself, one call
+		int calls = 0;
+		check(tei::dispatchBool(true, [&](auto b) { return calls++, (int) decltype(b)::value; }) == 1, "dispatchBool: true", 1, calls);
+		check(tei::dispatchBool(false, [&](auto b) { return calls++, (int) decltype(b)::value; }) == 0, "dispatchBool: false", 0, calls);
+		check(calls == 2, "dispatchBool: exactly one call each", 2, calls);
+	}
+}
 } // namespace
 
 int main()
@@ -132,6 +179,7 @@ int main()
 	checkRules<8>();
 	checkRules<16>();
 	checkRules<32>();
+	checkResweep();
 	if (failures) return 1;
 	std::printf("DISPATCH_OK\n");
 	return 0;

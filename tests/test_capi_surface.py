@@ -100,6 +100,15 @@ def test_set_option_and_release_workspace():
     with pytest.raises(capi.TeError) as e:
         g.set_option("TE_ZS_PIN", "3")
     assert e.value.code == capi.TE_EINVAL and g.slab_count(0) == 2
+    # TE_RESWEEP_V: 19, 27 or 59, the post-sweep variants a default reaches; a retired switch is an unknown option
+    with pytest.raises(capi.TeError) as e:
+        g.set_option("TE_RESWEEP_V", "31")
+    assert e.value.code == capi.TE_EINVAL
+    g.set_option("TE_RESWEEP_V", "59")
+    g.set_option("TE_RESWEEP_V", None)
+    with pytest.raises(capi.TeError) as e:
+        g.set_option("TE_NO_GTAB2", "1")
+    assert e.value.code == capi.TE_EINVAL
     from pressurepoissonsolver_amd import problems
     f, _ = problems.init_dirichlet(H.tables(0), 8)
     x = g.new_vector(0)

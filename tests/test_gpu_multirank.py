@@ -107,7 +107,7 @@ def test_sharded_ops_equal_single_rank(nranks, name, divides, n, dim, monkeypatc
 @pytest.mark.parametrize("nranks", [2, 8])
 def test_sharded_exported_ghost_terms(nranks, monkeypatch):
     """Two fused levels in a row (4096 and 512 patches): the ghost terms of the restricted residual are exported by
-    the patches that own the face values and gathered into the coarse level's side array (k_fcorr_gather3d); across a
+    the patches that own the face values and gathered into the coarse level's side array (k_fcorr_gather3d_v2); across a
     rank boundary they are formed from the ghost slots. Sharded == single rank == the fix-up pass (TE_NO_FCORR),
     bit for bit."""
     n = 4

@@ -161,14 +161,13 @@ def test_patch_solve_variants_agree(case, monkeypatch):
                                                 ("2refine.bin", 16, 3, False)])
 def test_exported_ghost_terms_gather_variants_bit_identical(mesh, n, div, neumann):
     """Two fused levels in a row: the ghost terms of the restricted residual reach the coarse level through k_fcorr_gather3d_v2
-    (round 6: per-level descriptors, 16-byte data loads only), through the kernel it replaces (TE_NO_GTAB2: a table word per entry on
-    uniform levels, the walk child -> face -> offset per entry on refined ones) or through the fix-up pass (TE_NO_FCORR): the same
-    bits. Uniform (finished sums of the neighbours) and refined (2x2 sums over face layers, copy-through patches) fine levels."""
+    (per-level descriptors, 16-byte data loads only), from the exported 2x2 sums or from the face layers (TE_NO_RS6_CF), or through
+    the fix-up pass (TE_NO_FCORR): the same bits. Uniform (finished sums of the neighbours) and refined (2x2 sums over face layers, copy-through patches) fine levels."""
     m, H, levels = util.setup(mesh, n, div, neumann=neumann, dim=3)
     g = capi.GMG(H)
     f = util.rand_vec(H.cells(0), 77) / levels[0].a["h"].min() ** 2
     got = {}
-    for name, opt in (("v2", None), ("v1", "TE_NO_GTAB2"), ("walk", "TE_NO_GTAB"), ("layers", "TE_NO_RS6_CF"), ("fixup", "TE_NO_FCORR"),
+    for name, opt in (("v2", None), ("layers", "TE_NO_RS6_CF"), ("fixup", "TE_NO_FCORR"),
                       ("fixup-layers", "TE_NO_FCORR,TE_NO_RS6_FIXUP")):  # (the fix-up pass from exported sums / from the face layers)
         for o1 in (opt.split(",") if opt else ()):
             g.set_option(o1, "1")
@@ -182,7 +181,7 @@ def test_exported_ghost_terms_gather_variants_bit_identical(mesh, n, div, neuman
             g.set_option(o1, None)
         assert ("fcorr_gather" in rows) == (not name.startswith("fixup")), (name, sorted(rows))
         got[name] = du.download()
-    for name in ("v1", "walk", "layers", "fixup", "fixup-layers"):
+    for name in ("layers", "fixup", "fixup-layers"):
         assert np.array_equal(got["v2"], got[name]), name
 
 
@@ -465,25 +464,21 @@ def test_fused_sums_of_the_stencil_kernel(case):
 
 
 def test_post_sweep_tuning_variants_bit_identical():
-    """k_rbgs_resweep_prolong3d's variants (TE_RESWEEP_V: which black values go back to LDS, when the top neighbour's plane is
-    loaded, non-temporal loads of f / stores of u, two / three / four ring slots for the planes of f in flight) and k_rbgs_zero_resid3d's prefetch distance (TE_ZR_AHEAD) change the
-    schedule, not one bit: 256^3 (the default there is 19) and the level-1 variant with exported ghost terms of a 16^3-patch
-    grid of 8^3 patches."""
+    """k_rbgs_resweep_prolong3d's variants (TE_RESWEEP_V: non-temporal loads of f / stores of u, two or four ring slots for the
+    planes of f in flight) change the schedule, not one bit: 256^3 (the default there is 19) and a 16^3-patch grid of 8^3
+    patches, whose level 1 reads exported ghost terms (always variant 3)."""
     for n, div in ((32, 3), (8, 4)):
         m, H, levels = util.setup("uniform", n, div)
         g = capi.GMG(H)
         f = util.rand_vec(levels[0].size, 88) / levels[0].a["h"].min() ** 2
         got = {}
-        for v in (None, "0", "3", "19", "27", "31", "59"):
+        for v in (None, "19", "27", "59"):
             g.set_option("TE_RESWEEP_V", v)
-            for ah in (None, "1"):
-                g.set_option("TE_ZR_AHEAD", ah)
-                df, du = g.new_vector(0, f), g.new_vector(0)
-                g.cycle(g.default_opts(smoother=capi.SMOOTH_RBGS), df, du)
-                got[(v, ah)] = du.download()
+            df, du = g.new_vector(0, f), g.new_vector(0)
+            g.cycle(g.default_opts(smoother=capi.SMOOTH_RBGS), df, du)
+            got[v] = du.download()
         g.set_option("TE_RESWEEP_V", None)
-        g.set_option("TE_ZR_AHEAD", None)
-        ref = got[(None, None)]
+        ref = got[None]
         for k, x in got.items():
             assert np.array_equal(x, ref), k
 
@@ -491,12 +486,12 @@ def test_post_sweep_tuning_variants_bit_identical():
 def test_refined_post_sweep_variants_bit_identical():
     """the recomputing post-sweep of a REFINED level (copy-through patches, coarse/fine ghost slots: k_rbgs_resweep_prolong3d<..., CFP>) in
     its three-workgroups-per-CU form (TE_RESWEEP_V=27; it spills nine registers) and in the two-workgroup form a large finest level
-    takes since round 6 (59: no spill; 1107 -> 1072 us per launch on `2refine --divide 3`; TE_NO_CFP59 = the former choice): same bits"""
+    takes since round 6 (59: no spill; 1107 -> 1072 us per launch on `2refine --divide 3`): same bits"""
     m, H, levels = util.setup("2refine.bin", 32, 2)
     g = capi.GMG(H)
     f = util.rand_vec(levels[0].size, 89) / levels[0].a["h"].min() ** 2
     got = {}
-    for name, opts in (("default", {}), ("v59", {"TE_RESWEEP_V": "59"}), ("v27", {"TE_RESWEEP_V": "27"}), ("no59", {"TE_RESWEEP_V": "59", "TE_NO_CFP59": "1"})):
+    for name, opts in (("default", {}), ("v59", {"TE_RESWEEP_V": "59"}), ("v27", {"TE_RESWEEP_V": "27"})):
         for k, v in opts.items():
             g.set_option(k, v)
         df, du = g.new_vector(0, f), g.new_vector(0)
@@ -509,7 +504,7 @@ def test_refined_post_sweep_variants_bit_identical():
             g.set_option(k, None)
         assert "rbgs_resweep_prolong" in rows, sorted(rows)
         got[name] = du.download()
-    for name in ("v59", "v27", "no59"):
+    for name in ("v59", "v27"):
         assert np.array_equal(got["default"], got[name]), name
     assert np.linalg.norm(got["default"] - orc.cycle(levels, orc.cycle_opts(smoother=capi.SMOOTH_RBGS), f)) <= 1e-10 * np.linalg.norm(got["default"])
 

@@ -61,8 +61,8 @@ def waits_in(body, s, e):
 
 CASES = [
     # mangled-name fragment, smallest vmcnt allowed inside the march, why
-    ("k_rbgs_zero_resid3dILi32ELb0ELb1ELb0ELi4ELi0E", 6, "pre-sweep, level 0: four planes of f in flight, three steps between request and use"),
-    ("k_rbgs_zero_resid3dILi32ELb0ELb0ELb1ELi4ELi0E", 6, "pre-sweep with exported ghost terms (level 1)"),
+    ("k_rbgs_zero_resid3dILi32ELb0ELb1ELb0ELi0E", 6, "pre-sweep, level 0: four planes of f in flight, three steps between request and use"),
+    ("k_rbgs_zero_resid3dILi32ELb0ELb0ELb1ELi0E", 6, "pre-sweep with exported ghost terms (level 1)"),
     ("k_rbgs_resweep_prolong3dILi32ELi27ELb0ELb0E", 2, "post-sweep, three workgroups per CU: the newest pair of f loads stays in flight"),
     ("k_rbgs_resweep_prolong3dILi32ELi59ELb0ELb0E", 2, "post-sweep at 512^3: two workgroups per CU, four slots"),
     ("k_rbgs_resweep_prolong3dILi32ELi3ELb1ELb0E", 2, "post-sweep with exported ghost terms (level 1)"),
@@ -84,9 +84,9 @@ def test_march_never_waits_for_its_newest_loads(isa, frag, floor, why):
 NO_SPILL = [  # every instantiation a default-option cycle or te_bicgstab launches on 32^3 patches (round 6: two of them spilled --
     # the pre-sweep that forms te_bicgstab's pending p and exports ghost terms, and the one that reads AND exports them -- with their
     # reloads inside the march, in the in-order queue of the planes in flight; they run two workgroups per CU now)
-    "k_rbgs_zero_resid3dILi32ELb0ELb1ELb0ELi4ELi0E", "k_rbgs_zero_resid3dILi32ELb0ELb1ELb0ELi4ELi1E", "k_rbgs_zero_resid3dILi32ELb0ELb1ELb0ELi4ELi2E",
-    "k_rbgs_zero_resid3dILi32ELb0ELb0ELb0ELi4ELi0E", "k_rbgs_zero_resid3dILi32ELb0ELb0ELb0ELi4ELi1E", "k_rbgs_zero_resid3dILi32ELb0ELb0ELb0ELi4ELi2E",
-    "k_rbgs_zero_resid3dILi32ELb0ELb0ELb1ELi4ELi0E", "k_rbgs_zero_resid3dILi32ELb0ELb1ELb1ELi4ELi0E", "k_rbgs_zero_resid3dILi32ELb1ELb0ELb0ELi4ELi0E",
+    "k_rbgs_zero_resid3dILi32ELb0ELb1ELb0ELi0E", "k_rbgs_zero_resid3dILi32ELb0ELb1ELb0ELi1E", "k_rbgs_zero_resid3dILi32ELb0ELb1ELb0ELi2E",
+    "k_rbgs_zero_resid3dILi32ELb0ELb0ELb0ELi0E", "k_rbgs_zero_resid3dILi32ELb0ELb0ELb0ELi1E", "k_rbgs_zero_resid3dILi32ELb0ELb0ELb0ELi2E",
+    "k_rbgs_zero_resid3dILi32ELb0ELb0ELb1ELi0E", "k_rbgs_zero_resid3dILi32ELb0ELb1ELb1ELi0E", "k_rbgs_zero_resid3dILi32ELb1ELb0ELb0ELi0E",
     "k_rbgs_resweep_prolong3dILi32ELi59ELb0ELb0E", "k_rbgs_resweep_prolong3dILi32ELi59ELb0ELb1E", "k_rbgs_resweep_prolong3dILi32ELi19ELb0ELb0E",
     "k_rbgs_resweep_prolong3dILi32ELi27ELb0ELb0E", "k_rbgs_resweep_prolong3dILi32ELi3ELb1ELb0E",
 ]
