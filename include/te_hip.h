@@ -635,11 +635,48 @@ int te_project(te_gmg *g, int level, double alpha, const te_vec *p, const te_vec
  *   contains "coefficient".
  *   te_gradient, te_divergence, te_project, te_restrict, the prolongations, the BLAS-1 calls, the boundary and the regrid calls never
  *   involve beta and are unchanged. te_add_boundary_rhs folds the CONSTANT-coefficient terms: with a coefficient the right-hand-side
- *   terms of boundary data are -te_divergence(1, beta (.) te_gradient(0, bdata)). */
+ *   terms of boundary data are -te_divergence(1, beta (.) te_gradient(0, bdata)).
+ *
+ * Every call of te_gmg_set_coefficient, with beta or with NULL, CLEARS the reaction term sigma (te_gmg_set_reaction below): the order
+ * per time step is beta, then sigma. */
 int te_faces_restrict(te_gmg *g, int fine_level, const te_vec *fine, te_vec *coarse);
 int te_gmg_set_coefficient(te_gmg *g, const te_vec *beta);
 int te_gmg_has_coefficient(const te_gmg *g);
 int te_gmg_coefficient(te_gmg *g, int level, te_vec *out);
+
+/* The reaction term: A_bs u = div(beta grad u) - sigma u, the operator of an implicit viscous or diffusive step
+ * (rho / dt) u - div(mu grad u) = rhs, in this library's sign convention div(mu grad u) - (rho / dt) u = -rhs: beta = mu,
+ * sigma = rho / dt, f = -rhs. sigma lives on the variable-coefficient path only. Single rank.
+ *
+ * sigma is a CELL vector of the level (te_vec_create's layout), every entry >= 0; nothing checks this, exactly as with beta.
+ *   operator   (A_bs u)[c] = (A_b u)[c] - sigma_c u_c: A_b evaluated exactly as written above, then one multiplication and one
+ *              subtraction. Residual r = f - A_bs u.
+ *   RB-GS      u_c <- (o - f_c) / (d + sigma_c), o and d as above; colour order and frozen ghosts unchanged.
+ *   Jacobi     u <- u + omega (f - A_bs u) / (-(d_J + sigma_c)).
+ *   coarse levels   level l + 1's sigma = te_restrict's average of level l's; a patch that copies through hands its block on bit
+ *              for bit.
+ *
+ * te_gmg_set_reaction: sigma = a level-0 cell vector of this solver (TE_EINVAL for a face, interface or boundary vector, another
+ * level's or another solver's). The solver COPIES it and restricts it to every level, into per-level cell vectors allocated at the
+ * first call and reused (a driver calls this every time step). NULL clears sigma and keeps the buffers. TE_ESTATE (the message says
+ * "coefficient") unless a coefficient is set; TE_ESTATE ("sharded") on a sharded hierarchy. A call that fails after its checks
+ * leaves NO sigma set. ORDER: every te_gmg_set_coefficient clears sigma, so per time step call te_gmg_set_coefficient first, then
+ * te_gmg_set_reaction -- the operator is always what the last calls said, never a new beta with a stale sigma.
+ * te_gmg_release_workspace frees the sigma buffers while sigma is cleared (and everything of the coefficient while that is
+ * cleared); te_gmg_destroy always.
+ * te_gmg_has_reaction: 0 or 1. te_gmg_reaction: out = the level's sigma (a cell vector of that level); TE_ESTATE when none is set.
+ *
+ * While sigma is set te_apply, te_residual, te_residual_norm_sq, te_smooth (RB-GS, Jacobi), te_vcycle (V and W, both interpolators)
+ * and te_bicgstab use A_bs; everything refused with a coefficient stays refused with the same codes. With sigma > 0 somewhere the
+ * all-Neumann problem is nonsingular.
+ *
+ * Constant viscosity, Laplace(u) - sigma u = f: create a face vector, te_vec_set(beta, 1.0), te_gmg_set_coefficient(g, beta), then
+ * te_gmg_set_reaction(g, sigma).
+ * Boundary data: sigma multiplies no ghost, so the right-hand-side terms of inhomogeneous data are those of A_b, unchanged:
+ * -te_divergence(1, beta (.) te_gradient(0, bdata)). */
+int te_gmg_set_reaction(te_gmg *g, const te_vec *sigma);
+int te_gmg_has_reaction(const te_gmg *g);
+int te_gmg_reaction(te_gmg *g, int level, te_vec *out);
 
 /* kernel timing hooks for bench.py: HIP-event time of the last te_vcycle's dominant kernel */
 int te_gmg_profile(te_gmg *g, int enable);

@@ -178,6 +178,9 @@ SYMBOLS = {
     "te_gmg_set_coefficient": (_I, [_P, _P]),
     "te_gmg_has_coefficient": (_I, [_P]),
     "te_gmg_coefficient": (_I, [_P, _I, _P]),
+    "te_gmg_set_reaction": (_I, [_P, _P]),
+    "te_gmg_has_reaction": (_I, [_P]),
+    "te_gmg_reaction": (_I, [_P, _I, _P]),
     "te_integrate": (_I, [_P, _I, _P, _P]),
     "te_volume": (_I, [_P, _I, _P]),
 }
@@ -601,7 +604,8 @@ class GMG:
 
     # ---- the variable-coefficient operator div(beta grad u) (te_hip.h: a second path, taken while a coefficient is set)
     def set_coefficient(self, beta):
-        """beta: a level-0 face vector (copied, then restricted to every level); None clears the coefficient"""
+        """beta: a level-0 face vector (copied, then restricted to every level); None clears the coefficient.
+        Every call clears the reaction term: per step set beta first, then sigma (set_reaction)."""
         check(lib().te_gmg_set_coefficient(self.h, beta.h if beta is not None else None))
 
     def has_coefficient(self):
@@ -610,6 +614,19 @@ class GMG:
     def coefficient(self, level, out):
         """out (a face vector of `level`) = the solver's beta on that level"""
         check(lib().te_gmg_coefficient(self.h, level, out.h))
+
+    # ---- the reaction term: div(beta grad u) - sigma u (te_hip.h te_gmg_set_reaction; only while a coefficient is set)
+    def set_reaction(self, sigma):
+        """sigma: a level-0 cell vector, every entry >= 0 (copied, then restricted to every level); None clears it.
+        After set_coefficient, never before: set_coefficient clears sigma."""
+        check(lib().te_gmg_set_reaction(self.h, sigma.h if sigma is not None else None))
+
+    def has_reaction(self):
+        return bool(lib().te_gmg_has_reaction(self.h))
+
+    def reaction(self, level, out):
+        """out (a cell vector of `level`) = the solver's sigma on that level"""
+        check(lib().te_gmg_reaction(self.h, level, out.h))
 
     def faces_restrict(self, fine_level, fine, coarse):
         """coarse (a face vector of fine_level + 1) = the face average of fine"""

@@ -23,6 +23,11 @@
 // l's -- te_faces_regrid's "coarsen" rule (faceregridkernels.hpp coarsenPairX / coarsenPairT / face2d) through the level's child / copy
 // tables. One writer per entry; a patch that copies through hands its block on bit for bit.
 //
+// The reaction term: every operator / sweep kernel has a compile-time SIG and a pointer to the level's cell
+// vector sigma >= 0. SIG = true: apply (A_b u)[c] - sigma_c u_c (A_b as above, then one multiplication and one subtraction), residual
+// f - that, Jacobi's diagonal d_J + sigma_c, RB-GS's d + sigma_c. Every load and use of sigma sits under `if constexpr (SIG)`:
+// SIG = false is the code as it was before the term existed.
+//
 // FMA contraction is off for this file (it is included behind faceregridkernels.hpp, whose pragma holds to the end of the unit): the
 // sums above are evaluated as written.
 #pragma once
@@ -98,9 +103,9 @@ __device__ __forceinline__ void coefCell2d(const CoefLevel &L, const double *__r
 	}
 }
 
-template <int MODE>
+template <int MODE, bool SIG = false>
 __global__ __launch_bounds__(256) void k_coef_stencil2d(CoefLevel L, const double *__restrict__ u, const double *__restrict__ f,
-                                                      double *__restrict__ out, double omega)
+                                                      double *__restrict__ out, double omega, const double *__restrict__ sigma = nullptr)
 {
 	const int    nc = L.n * L.n;
 	const size_t total = (size_t) L.P * nc;
@@ -109,6 +114,11 @@ __global__ __launch_bounds__(256) void k_coef_stencil2d(CoefLevel L, const doubl
 		const double m = u[idx];
 		double       au, dj;
 		coefCell2d<false>(L, u, u + (size_t) p * nc, p, c, m, au, dj);
+		if constexpr (SIG) { // A_b,sigma u = A_b u - sigma u; the Jacobi diagonal d_J + sigma
+			const double sg = sigma[idx];
+			au              = au - sg * m;
+			dj              = dj + sg;
+		}
 		if (MODE == COEF_APPLY)
 			out[idx] = au;
 		else if (MODE == COEF_RESID)
@@ -128,9 +138,14 @@ __global__ __launch_bounds__(256) void k_coef_stencil2d(CoefLevel L, const doubl
 // k_divergence3d. Nothing a step requests is consumed by the same step; every load of the loop is unconditional, from a pointer and
 // stride chosen before the loop. Algorithmic bytes per site at N = 32: u 8 + 6/32 * 8 = 9.5, beta 24.75, out 8 -> 42.25 (apply),
 // + 8 for f -> 50.25 (residual, Jacobi).
-template <int N, int MODE, int ZS>
+//
+// SIG (te_gmg_set_reaction): the cell vector sigma rides along exactly as f does -- the thread's own two
+// pairs of plane z + 2 requested in the refill, consumed two steps later; (A_b u)[c] - sigma_c u_c, the Jacobi diagonal d_J + sigma_c.
+// + 8 B/site. Every load and use of sigma sits under `if constexpr (SIG)`: SIG = false is the kernel as it was.
+template <int N, int MODE, int ZS, bool SIG = false>
 __global__ __launch_bounds__(Tile3<N>::TPB) void k_coef_stencil3d(LevelDev L, const double *__restrict__ beta, const double *__restrict__ u,
-                                                                  const double *__restrict__ f, double *__restrict__ out, double omega)
+                                                                  const double *__restrict__ f, double *__restrict__ out, double omega,
+                                                                  const double *__restrict__ sigma = nullptr)
 {
 	using T           = Tile3<N>;
 	constexpr int TPB = T::TPB, NP = T::NP, H = T::H;
@@ -155,6 +170,7 @@ __global__ __launch_bounds__(Tile3<N>::TPB) void k_coef_stencil3d(LevelDev L, co
 	const double2 *up2 = reinterpret_cast<const double2 *>(up);
 	const double2 *fp2 = reinterpret_cast<const double2 *>((HAS_F ? f : u) + (size_t) pid * NNN);
 	double2       *op2 = reinterpret_cast<double2 *>(out + (size_t) pid * NNN);
+	const double2 *sp2 = reinterpret_cast<const double2 *>((SIG ? sigma : u) + (size_t) pid * NNN);
 	const double2 *lo2 = reinterpret_cast<const double2 *>(beta + (size_t) pid * FV);                    // LO_a plane z: lo2[a * NNN / 2 + z * NP + q]
 	const double2 *hi2 = reinterpret_cast<const double2 *>(beta + (size_t) pid * FV + 3 * (size_t) NNN); // HI_a: hi2[a * NN / 2 + ...]
 
@@ -188,8 +204,8 @@ __global__ __launch_bounds__(Tile3<N>::TPB) void k_coef_stencil3d(LevelDev L, co
 	const PlaneSrc bot = zPlaneSrc<N>(fk[4], fs[4], false, u, up, L.ghost, -1.0, 1.0);
 	const PlaneSrc top = zPlaneSrc<N>(fk[5], fs[5], true, u, up, L.ghost, -1.0, 1.0);
 
-	double2 um[2], uc[2], un[2], fc[2];
-	double2 ur[2][2], fr[2][2];
+	double2 um[2], uc[2], un[2], fc[2], sc[2];
+	double2 ur[2][2], fr[2][2], sr[2][2];
 	double2 bx[2], by[2], bzc[2], bzn[2], Rx[2], Ry[2], Rz[2], Rhx, Rhy, hx, hy;
 	auto uPlane = [&](int p) { return (p < 0) ? bot.p : (p < N ? up2 + p * NP : top.p); }; // p = z0 - 1 .. N
 	auto uScale = [&](int p) { return (p < 0) ? bot.s : (p < N ? 1.0 : top.s); };
@@ -211,6 +227,7 @@ __global__ __launch_bounds__(Tile3<N>::TPB) void k_coef_stencil3d(LevelDev L, co
 		for (int k = 0; k < 2; k++) {
 			ur[(i + 1) & 1][k] = uPlane(z0 + 1 + i)[q[k]];
 			if (HAS_F) fr[i][k] = fp2[clampP(z0 + i) * NP + q[k]];
+			if constexpr (SIG) sr[i][k] = sp2[clampP(z0 + i) * NP + q[k]];
 		}
 		__builtin_amdgcn_sched_barrier(0);
 	}
@@ -241,6 +258,7 @@ __global__ __launch_bounds__(Tile3<N>::TPB) void k_coef_stencil3d(LevelDev L, co
 			const double2 a = takeRegs(ur[1 - PAR][k]); // plane z + 1
 			un[k]           = double2{sn * a.x, sn * a.y};
 			if (HAS_F) fc[k] = takeRegs(fr[PAR][k]);
+			if constexpr (SIG) sc[k] = takeRegs(sr[PAR][k]);
 			bx[k]  = takeRegs(Rx[k]);
 			by[k]  = takeRegs(Ry[k]);
 			bzc[k] = bzn[k];
@@ -248,6 +266,7 @@ __global__ __launch_bounds__(Tile3<N>::TPB) void k_coef_stencil3d(LevelDev L, co
 			if (REFILL) {
 				ur[1 - PAR][k] = uPlane(z + 3)[q[k]];
 				if (HAS_F) fr[PAR][k] = fp2[clampP(z + 2) * NP + q[k]];
+				if constexpr (SIG) sr[PAR][k] = sp2[clampP(z + 2) * NP + q[k]];
 				Rz[k] = zPl(z + 2)[q[k]];
 			}
 			if (REFILL || PAR == 0) {
@@ -296,6 +315,10 @@ __global__ __launch_bounds__(Tile3<N>::TPB) void k_coef_stencil3d(LevelDev L, co
 			a.y += (bh.y * (yp.y - c.y) - bl.y * (c.y - ym.y)) * rhy;
 			a.x += (bzn[k].x * (un[k].x - c.x) - bzc[k].x * (c.x - um[k].x)) * rhz;
 			a.y += (bzn[k].y * (un[k].y - c.y) - bzc[k].y * (c.y - um[k].y)) * rhz;
+			if constexpr (SIG) {
+				a.x = a.x - sc[k].x * c.x;
+				a.y = a.y - sc[k].y * c.y;
+			}
 			if (MODE == COEF_APPLY) {
 				r[k] = a;
 			} else if (MODE == COEF_RESID) {
@@ -316,6 +339,10 @@ __global__ __launch_bounds__(Tile3<N>::TPB) void k_coef_stencil3d(LevelDev L, co
 				d.x += bzn[k].x * wt * rhz;
 				d.y += bzc[k].y * wb * rhz;
 				d.y += bzn[k].y * wt * rhz;
+				if constexpr (SIG) {
+					d.x = d.x + sc[k].x;
+					d.y = d.y + sc[k].y;
+				}
 				r[k].x = c.x + omega * (fc[k].x - a.x) / (-d.x);
 				r[k].y = c.y + omega * (fc[k].y - a.y) / (-d.y);
 			}
@@ -344,8 +371,9 @@ __global__ __launch_bounds__(Tile3<N>::TPB) void k_coef_stencil3d(LevelDev L, co
 }
 
 // PHASE 0: red cells relaxed from u, black cells copied; PHASE 1: black cells relaxed in `out` from the new red values there
-template <int PHASE>
-__global__ __launch_bounds__(256) void k_coef_rbgs2d(CoefLevel L, const double *__restrict__ u, const double *__restrict__ f, double *out)
+template <int PHASE, bool SIG = false>
+__global__ __launch_bounds__(256) void k_coef_rbgs2d(CoefLevel L, const double *__restrict__ u, const double *__restrict__ f, double *out,
+                                                     const double *__restrict__ sigma = nullptr)
 {
 	const int    n = L.n, nc = n * n;
 	const size_t total = (size_t) L.P * nc;
@@ -358,6 +386,7 @@ __global__ __launch_bounds__(256) void k_coef_rbgs2d(CoefLevel L, const double *
 		}
 		double o, d;
 		coefCell2d<true>(L, u, (PHASE == 0 ? u : out) + (size_t) p * nc, p, c, 0.0, o, d);
+		if constexpr (SIG) d = d + sigma[idx];
 		out[idx] = (o - f[idx]) / d;
 	}
 }
@@ -372,12 +401,19 @@ __global__ __launch_bounds__(256) void k_coef_rbgs2d(CoefLevel L, const double *
 // requested one step ahead and kept for two steps (red of plane z, black of plane z at the next step); LO_z runs as a chain of
 // four planes z - 1 .. z + 2, HI_z above the last. Every load of the loop is unconditional, from a pointer and stride chosen
 // before the loop. d is formed per cell from the same planes (no table: it depends on beta).
+//
+// SIG (te_gmg_set_reaction): d + sigma_c in both updates. sigma runs beside f as gm / gc (planes z - 1, z): the
+// red update of plane z and, one step later, the black update of the same plane read it. The pairs of plane z + 1 are requested at the
+// END of step z, when those of plane z - 1 are dead, and consumed by step z + 1: two planes of sigma are live during the updates, not
+// three (a third, requested at the top of the step as f's is, puts EVERY instantiation past 256 registers and at one wave per SIMD;
+// this form only the ZS = 1 ones of N >= 8). The slab rule is unchanged. + 8 B/site. SIG = false is the kernel as it was.
 struct BetaPlane {
 	double2 bx[2], by[2], byu, hx; // LO_x, LO_y of the two rows; LO_y of the row above the pair / HI_y; HI_x of the two rows (east threads)
 };
-template <int N, int ZS>
+template <int N, int ZS, bool SIG = false>
 __global__ __launch_bounds__(Tile3<N>::TPB) void k_coef_rbgs3d(LevelDev L, const double *__restrict__ beta, const double *__restrict__ u,
-                                                               const double *__restrict__ f, double *__restrict__ out)
+                                                               const double *__restrict__ f, double *__restrict__ out,
+                                                               const double *__restrict__ sigma = nullptr)
 {
 	using T           = Tile3<N>;
 	constexpr int TPB = T::TPB, NP = T::NP, H = T::H;
@@ -402,6 +438,7 @@ __global__ __launch_bounds__(Tile3<N>::TPB) void k_coef_rbgs3d(LevelDev L, const
 	const double2 *up2 = reinterpret_cast<const double2 *>(up);
 	const double2 *fp2 = reinterpret_cast<const double2 *>(f + (size_t) pid * NNN);
 	double2       *op2 = reinterpret_cast<double2 *>(out + (size_t) pid * NNN);
+	const double2 *sp2 = reinterpret_cast<const double2 *>((SIG ? sigma : u) + (size_t) pid * NNN);
 	const double2 *lo2 = reinterpret_cast<const double2 *>(beta + (size_t) pid * FV);
 	const double2 *hi2 = reinterpret_cast<const double2 *>(beta + (size_t) pid * FV + 3 * (size_t) NNN);
 
@@ -442,6 +479,7 @@ __global__ __launch_bounds__(Tile3<N>::TPB) void k_coef_rbgs3d(LevelDev L, const
 	// planes: umm = z-2, um = z-1, uc = z, un = z+1, un2 = z+2 (values are updated in place); start at z = zs
 	double2   umm[2], um[2], uc[2], un[2], un2[2], fm[2], fc[2], fn[2];
 	double2   zm[2], zc[2], zn[2], zn2[2]; // LO_z of planes z-1, z, z+1, z+2
+	double2   gm[2], gc[2];                // SIG: sigma of planes z-1, z
 	BetaPlane Bm, Bc, Bn;
 	double    bxeM[2] = {0.0, 0.0}, bxeC[2];
 #pragma unroll
@@ -455,6 +493,10 @@ __global__ __launch_bounds__(Tile3<N>::TPB) void k_coef_rbgs3d(LevelDev L, const
 		fc[k]     = fp2[zs * NP + q[k]];
 		umm[k]    = double2{0.0, 0.0};
 		fm[k]     = double2{0.0, 0.0};
+		if constexpr (SIG) {
+			gc[k] = sp2[zs * NP + q[k]];
+			gm[k] = double2{0.0, 0.0};
+		}
 		zc[k]     = zPlane(zs)[q[k]];
 		zn[k]     = zPlane(zs + 1)[q[k]];
 		zm[k]     = double2{0.0, 0.0};
@@ -465,7 +507,8 @@ __global__ __launch_bounds__(Tile3<N>::TPB) void k_coef_rbgs3d(LevelDev L, const
 
 	// relax cell CB (0: even x, 1: odd x) of row K of plane Z held in `cen` (LDS copy in tl): v = (o - f) / d
 	auto relax = [&](auto kk, auto cbb, double *tl, int Z, double2(&cen)[2], const double2(&below)[2], const double2(&above)[2],
-	                 const double2(&rhs)[2], const BetaPlane &B, const double(&bxe)[2], const double2(&zlo)[2], const double2(&zhi)[2]) {
+	                 const double2(&rhs)[2], const BetaPlane &B, const double(&bxe)[2], const double2(&zlo)[2], const double2(&zhi)[2],
+	                 const double2(&sig)[2]) {
 		constexpr int K = decltype(kk)::value, CB = decltype(cbb)::value;
 		auto          c = [&](const double2 &v) { return CB ? v.y : v.x; };
 		const double side  = CB ? tl[lds[K] + 2] : tl[lds[K] - 1]; // the x-neighbour outside the pair
@@ -491,6 +534,7 @@ __global__ __launch_bounds__(Tile3<N>::TPB) void k_coef_rbgs3d(LevelDev L, const
 		d += byh * wyh * rhy;
 		d += bzl * wzl * rhz;
 		d += bzh * wzh * rhz;
+		if constexpr (SIG) d = d + c(sig[K]);
 		const double v = (o - c(rhs[K])) / d;
 		if (CB)
 			cen[K].y = v;
@@ -535,12 +579,12 @@ __global__ __launch_bounds__(Tile3<N>::TPB) void k_coef_rbgs3d(LevelDev L, const
 		bxeC[0] = east ? Bc.hx.x : n0;
 		bxeC[1] = east ? Bc.hx.y : n1;
 		if (z < N) { // red cells of plane z from old black values: cell parity = (0 + k + z) & 1
-			relax(I0{}, std::integral_constant<int, (0 + ZPAR) & 1>{}, tz, z, uc, um, un, fc, Bc, bxeC, zc, zn);
-			relax(I1{}, std::integral_constant<int, (1 + ZPAR) & 1>{}, tz, z, uc, um, un, fc, Bc, bxeC, zc, zn);
+			relax(I0{}, std::integral_constant<int, (0 + ZPAR) & 1>{}, tz, z, uc, um, un, fc, Bc, bxeC, zc, zn, gc);
+			relax(I1{}, std::integral_constant<int, (1 + ZPAR) & 1>{}, tz, z, uc, um, un, fc, Bc, bxeC, zc, zn, gc);
 		}
 		if (z > z0) { // black cells of plane z-1 from new red values (the plane below a slab only lends its red values)
-			relax(I0{}, std::integral_constant<int, (1 + 0 + 1 - ZPAR) & 1>{}, tm, z - 1, um, umm, uc, fm, Bm, bxeM, zm, zc);
-			relax(I1{}, std::integral_constant<int, (1 + 1 + 1 - ZPAR) & 1>{}, tm, z - 1, um, umm, uc, fm, Bm, bxeM, zm, zc);
+			relax(I0{}, std::integral_constant<int, (1 + 0 + 1 - ZPAR) & 1>{}, tm, z - 1, um, umm, uc, fm, Bm, bxeM, zm, zc, gm);
+			relax(I1{}, std::integral_constant<int, (1 + 1 + 1 - ZPAR) & 1>{}, tm, z - 1, um, umm, uc, fm, Bm, bxeM, zm, zc, gm);
 			if (act) {
 				op2[(z - 1) * NP + q[0]] = um[0];
 				op2[(z - 1) * NP + q[1]] = um[1];
@@ -554,6 +598,10 @@ __global__ __launch_bounds__(Tile3<N>::TPB) void k_coef_rbgs3d(LevelDev L, const
 			un[k]  = un2[k];
 			fm[k]  = fc[k];
 			fc[k]  = fn[k];
+			if constexpr (SIG) {
+				gm[k] = gc[k];
+				gc[k] = sp2[zc1 * NP + q[k]]; // plane z + 1, for the next step
+			}
 			zm[k]  = zc[k];
 			zc[k]  = zn[k];
 			zn[k]  = zn2[k];
@@ -577,8 +625,9 @@ __global__ __launch_bounds__(Tile3<N>::TPB) void k_coef_rbgs3d(LevelDev L, const
 // LDS, both colours in one launch, as k_rbgs2d_lds. The ring holds the frozen ghosts of the old iterate (0 on physical faces);
 // the same sums, in the same order, as k_coef_rbgs2d<0> + <1>. beta and f come from global memory (every entry is read by the one
 // or two cells that use it). Dynamic LDS: (n + 2)^2 doubles.
+template <bool SIG = false>
 static __global__ __launch_bounds__(256) void k_coef_rbgs2d_lds(CoefLevel L, const double *__restrict__ u, const double *__restrict__ f,
-                                                                double *__restrict__ out)
+                                                                double *__restrict__ out, const double *__restrict__ sigma = nullptr)
 {
 	extern __shared__ double t2[];
 	const int     n = L.n, nn = n * n, W = n + 2, h = n / 2, p = blockIdx.x, tid = threadIdx.x, TPB = blockDim.x;
@@ -616,6 +665,7 @@ static __global__ __launch_bounds__(256) void k_coef_rbgs2d_lds(CoefLevel L, con
 			d += bxh * (x == n - 1 ? kap[1] : 1.0) * rhx;
 			d += byl * (y == 0 ? kap[2] : 1.0) * rhy;
 			d += byh * (y == n - 1 ? kap[3] : 1.0) * rhy;
+			if constexpr (SIG) d = d + sigma[(size_t) p * nn + c];
 			tc[0] = (o - fp[c]) / d;
 		}
 		__syncthreads();

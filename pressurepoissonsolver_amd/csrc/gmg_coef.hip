@@ -2,23 +2,51 @@
 // copy of the coefficient on every level (te_gmg_set_coefficient, te_faces_restrict), the operator, residual and sweeps that te_apply /
 // te_residual / te_smooth hand over while a coefficient is set, and the plain cycle driver visitCoef behind te_vcycle. A second,
 // unfused path: nothing here touches the kernels or the driver of the constant-coefficient one. Single rank.
+// The reaction term sigma (te_gmg_set_reaction) lives here too: per-level cell vectors beside beta's, and every
+// launch below picks its kernel's SIG instantiation by g->coef->sigma_on -- A_b,sigma = A_b - sigma in operator, residual and sweeps.
 #include "gmg_ghosts3d.hpp"
 #include "coefkernels.hpp" // (with faceregridkernels.hpp: the LAST include, FMA contraction is off from there on)
 
 struct CoefWs {
-	std::vector<te_vec *> beta; // [level] face vectors of the solver
+	std::vector<te_vec *> beta;  // [level] face vectors of the solver
+	std::vector<te_vec *> sigma; // [level] cell vectors of the solver: the reaction term (te_gmg_set_reaction); empty until the first call
+	bool                  sigma_on = false; // the operator is A_b,sigma = A_b - sigma
 };
 
 namespace tei
 {
+static void sigmaFree(CoefWs *W)
+{
+	for (te_vec *v : W->sigma)
+		if (v) te_vec_destroy(v);
+	W->sigma.clear();
+	W->sigma_on = false;
+}
+
 void coefFree(te_gmg *g)
 {
 	if (!g->coef) return;
+	sigmaFree(g->coef);
 	for (te_vec *v : g->coef->beta)
 		if (v) te_vec_destroy(v);
 	delete g->coef;
 	g->coef    = nullptr;
 	g->coef_on = false;
+}
+
+// te_gmg_release_workspace: everything while no coefficient is set; with one set, the sigma buffers while sigma is cleared
+void coefRelease(te_gmg *g)
+{
+	if (!g->coef_on)
+		coefFree(g);
+	else if (g->coef && !g->coef->sigma_on)
+		sigmaFree(g->coef);
+}
+
+// the level's sigma while one is set, else nullptr (the launches pick their SIG instantiation by it)
+static const double *sigmaOf(const te_gmg *g, const LevelHost &L)
+{
+	return g->coef->sigma_on ? g->coef->sigma[L.index]->d : nullptr;
 }
 
 static int checkFaces(te_gmg *g, int level, const te_vec *v, const char *who)
@@ -71,27 +99,32 @@ static int coefGhosts(te_gmg *g, LevelHost &L, const double *u)
 	return dispatchN(L.n, [&](auto n) { return prepareGhosts<decltype(n)::value>(g, L, GhostSrc{u}); });
 }
 
-static void stencil2d(te_gmg *g, const CoefLevel &C, dim3 grid, int mode, const double *u, const double *f, double *out, double omega)
+template <bool SIG>
+static void stencil2d(te_gmg *g, const CoefLevel &C, dim3 grid, int mode, const double *u, const double *f, double *out, double omega, const double *sigma)
 {
 	if (mode == COEF_APPLY)
-		hipLaunchKernelGGL(k_coef_stencil2d<COEF_APPLY>, grid, dim3(256), 0, g->stream, C, u, f, out, omega);
+		hipLaunchKernelGGL((k_coef_stencil2d<COEF_APPLY, SIG>), grid, dim3(256), 0, g->stream, C, u, f, out, omega, sigma);
 	else if (mode == COEF_RESID)
-		hipLaunchKernelGGL(k_coef_stencil2d<COEF_RESID>, grid, dim3(256), 0, g->stream, C, u, f, out, omega);
+		hipLaunchKernelGGL((k_coef_stencil2d<COEF_RESID, SIG>), grid, dim3(256), 0, g->stream, C, u, f, out, omega, sigma);
 	else
-		hipLaunchKernelGGL(k_coef_stencil2d<COEF_JACOBI>, grid, dim3(256), 0, g->stream, C, u, f, out, omega);
+		hipLaunchKernelGGL((k_coef_stencil2d<COEF_JACOBI, SIG>), grid, dim3(256), 0, g->stream, C, u, f, out, omega, sigma);
 }
 
 // 3D: the plane march k_coef_stencil3d<N, MODE, ZS>, slabs by the stencil kernels' rule, ghosts through withGhosts as for te_apply
 template <int N, int MODE> static int coefStencilN(te_gmg *g, LevelHost &L, const double *u, const double *f, double *out, double omega)
 {
 	const int     zs   = stencilSlabs<N>(g, L.P);
-	const double *beta = g->coef->beta[L.index]->d;
+	const double *beta = g->coef->beta[L.index]->d, *sigma = sigmaOf(g, L);
 	auto          launch = [&](LevelDev D) {
 		if (D.count == 0) return;
 		Timed t(g, MODE == COEF_APPLY ? KC_APPLY_COEF : (MODE == COEF_RESID ? KC_RESID_COEF : KC_JACOBI_COEF), (size_t) D.count * L.nc);
 		dispatchSlabs<N>(zs, [&](auto z) {
-			hipLaunchKernelGGL((k_coef_stencil3d<N, MODE, decltype(z)::value>), slabGrid(D.count, zs), dim3(Tile3<N>::TPB), 0, g->stream, D, beta, u, f,
-			                   out, omega);
+			if (sigma)
+				hipLaunchKernelGGL((k_coef_stencil3d<N, MODE, decltype(z)::value, true>), slabGrid(D.count, zs), dim3(Tile3<N>::TPB), 0, g->stream, D,
+				                   beta, u, f, out, omega, sigma);
+			else
+				hipLaunchKernelGGL((k_coef_stencil3d<N, MODE, decltype(z)::value, false>), slabGrid(D.count, zs), dim3(Tile3<N>::TPB), 0, g->stream, D,
+				                   beta, u, f, out, omega, sigma);
 		});
 	};
 	int rc = withGhosts<N>(g, L, {u}, launch);
@@ -116,7 +149,10 @@ int coefStencil(te_gmg *g, LevelHost &L, int mode, const double *u, const double
 	if (rc) return rc;
 	Timed      t(g, mode == COEF_APPLY ? KC_APPLY_COEF : (mode == COEF_RESID ? KC_RESID_COEF : KC_JACOBI_COEF), (size_t) L.P * L.nc);
 	const dim3 grid(gridFor((size_t) L.P * L.nc, 256, 1 << 30)); // (one cell per thread: a flat grid in address order, see vecop)
-	stencil2d(g, coefLevel(g, L), grid, mode, u, f, out, omega);
+	if (const double *sigma = sigmaOf(g, L))
+		stencil2d<true>(g, coefLevel(g, L), grid, mode, u, f, out, omega, sigma);
+	else
+		stencil2d<false>(g, coefLevel(g, L), grid, mode, u, f, out, omega, nullptr);
 	HIPCHK(hipGetLastError());
 	return TE_OK;
 }
@@ -124,13 +160,18 @@ int coefStencil(te_gmg *g, LevelHost &L, int mode, const double *u, const double
 // 3D: the lagged single-pass march k_coef_rbgs3d<N, ZS>, slabs by the sweep kernels' rule
 template <int N> static int coefRbgsN(te_gmg *g, LevelHost &L, const double *u, const double *f, double *out)
 {
-	const double *beta = g->coef->beta[L.index]->d;
+	const double *beta = g->coef->beta[L.index]->d, *sigma = sigmaOf(g, L);
 	auto          launch = [&](LevelDev D) {
 		if (D.count == 0) return;
 		const int zs = rbgsSlabs<N>(g, D.count);
 		Timed     t(g, KC_RBGS_COEF, (size_t) D.count * L.nc);
 		dispatchSlabs<N>(zs, [&](auto z) {
-			hipLaunchKernelGGL((k_coef_rbgs3d<N, decltype(z)::value>), slabGrid(D.count, zs), dim3(Tile3<N>::TPB), 0, g->stream, D, beta, u, f, out);
+			if (sigma)
+				hipLaunchKernelGGL((k_coef_rbgs3d<N, decltype(z)::value, true>), slabGrid(D.count, zs), dim3(Tile3<N>::TPB), 0, g->stream, D, beta, u,
+				                   f, out, sigma);
+			else
+				hipLaunchKernelGGL((k_coef_rbgs3d<N, decltype(z)::value, false>), slabGrid(D.count, zs), dim3(Tile3<N>::TPB), 0, g->stream, D, beta, u,
+				                   f, out, sigma);
 		});
 	};
 	int rc = withGhosts<N>(g, L, {u}, launch);
@@ -149,13 +190,22 @@ static int coefRbgs(te_gmg *g, LevelHost &L, const double *u, const double *f, d
 	if (rc) return rc;
 	Timed           t(g, KC_RBGS_COEF, (size_t) L.P * L.nc);
 	const CoefLevel C = coefLevel(g, L);
-	if (L.n <= 64) { // the patch and its ring fit in LDS: both colours in one launch
-		hipLaunchKernelGGL(k_coef_rbgs2d_lds, dim3(L.P), dim3(256), sizeof(double) * (size_t) (L.n + 2) * (L.n + 2), g->stream, C, u, f, out);
-	} else {
-		const dim3 grid(gridFor((size_t) L.P * L.nc, 256, 1 << 30));
-		hipLaunchKernelGGL(k_coef_rbgs2d<0>, grid, dim3(256), 0, g->stream, C, u, f, out);
-		hipLaunchKernelGGL(k_coef_rbgs2d<1>, grid, dim3(256), 0, g->stream, C, u, f, out);
-	}
+	const double   *sigma = sigmaOf(g, L);
+	auto            launch = [&](auto sig) {
+		constexpr bool SIG = decltype(sig)::value;
+		if (L.n <= 64) { // the patch and its ring fit in LDS: both colours in one launch
+			hipLaunchKernelGGL(k_coef_rbgs2d_lds<SIG>, dim3(L.P), dim3(256), sizeof(double) * (size_t) (L.n + 2) * (L.n + 2), g->stream, C, u, f, out,
+			                   sigma);
+		} else {
+			const dim3 grid(gridFor((size_t) L.P * L.nc, 256, 1 << 30));
+			hipLaunchKernelGGL((k_coef_rbgs2d<0, SIG>), grid, dim3(256), 0, g->stream, C, u, f, out, sigma);
+			hipLaunchKernelGGL((k_coef_rbgs2d<1, SIG>), grid, dim3(256), 0, g->stream, C, u, f, out, sigma);
+		}
+	};
+	if (sigma)
+		launch(std::true_type{});
+	else
+		launch(std::false_type{});
 	HIPCHK(hipGetLastError());
 	return TE_OK;
 }
@@ -244,6 +294,7 @@ int te_gmg_set_coefficient(te_gmg *g, const te_vec *beta)
 		int rc;
 		if (!g) return te::fail(TE_EINVAL, "te_gmg_set_coefficient: null solver");
 		for (auto &L : g->levels) L->xf_valid_for = nullptr; // (the operator changes)
+		if (g->coef) g->coef->sigma_on = false; // every call clears sigma: never a new beta with a stale sigma (the order per step is beta, then sigma)
 		if (!beta) { // (also on a sharded hierarchy, where none can be set: nothing to clear)
 			g->coef_on = false;
 			return TE_OK;
@@ -284,6 +335,58 @@ int te_gmg_coefficient(te_gmg *g, int level, te_vec *out)
 		if (!g->coef_on || !g->coef) return te::fail(TE_ESTATE, "te_gmg_coefficient: no coefficient is set");
 		if ((rc = checkFaces(g, level, out, "te_gmg_coefficient"))) return rc;
 		if (out->n) HIPCHK(hipMemcpyAsync(out->d, g->coef->beta[level]->d, sizeof(double) * out->n, hipMemcpyDeviceToDevice, g->stream));
+		return TE_OK;
+	});
+}
+
+int te_gmg_set_reaction(te_gmg *g, const te_vec *sigma)
+{
+	return guarded([&]() -> int {
+		int rc;
+		if (!g) return te::fail(TE_EINVAL, "te_gmg_set_reaction: null solver");
+		for (auto &L : g->levels) L->xf_valid_for = nullptr; // (the operator changes)
+		if (!sigma) { // (also where none can be set: nothing to clear)
+			if (g->coef) g->coef->sigma_on = false;
+			return TE_OK;
+		}
+		if ((rc = refuseSharded(g, "te_gmg_set_reaction"))) return rc;
+		if (!g->coef_on || !g->coef)
+			return te::fail(TE_ESTATE, "te_gmg_set_reaction: no coefficient is set (sigma lives on the coefficient path: te_gmg_set_coefficient first, "
+			                           "a face vector of ones for the Laplacian)");
+		if ((rc = checkLevelVec(g, 0, sigma, "te_gmg_set_reaction"))) return rc;
+		const int nl = (int) g->levels.size();
+		auto     &S  = g->coef->sigma;
+		// from here on the per-level copies are being rewritten: a failure leaves NO sigma set
+		g->coef->sigma_on = false;
+		if (S.empty()) {
+			S.assign(nl, nullptr);
+			for (int l = 0; l < nl; l++)
+				if ((rc = te_vec_create(g, l, &S[l]))) {
+					sigmaFree(g->coef);
+					return rc;
+				}
+		}
+		if (sigma->n) HIPCHK(hipMemcpyAsync(S[0]->d, sigma->d, sizeof(double) * sigma->n, hipMemcpyDeviceToDevice, g->stream));
+		for (int l = 0; l + 1 < nl; l++)
+			if ((rc = doRestrict(g, l, S[l]->d, S[l + 1]->d))) return rc; // te_restrict's average; copy-through patches bit for bit
+		g->coef->sigma_on = true;
+		return TE_OK;
+	});
+}
+
+int te_gmg_has_reaction(const te_gmg *g)
+{
+	return guarded([&]() -> int { return (g && g->coef_on && g->coef && g->coef->sigma_on) ? 1 : 0; });
+}
+
+int te_gmg_reaction(te_gmg *g, int level, te_vec *out)
+{
+	return guarded([&]() -> int {
+		int rc;
+		if (!g) return te::fail(TE_EINVAL, "te_gmg_reaction: null solver");
+		if (!g->coef_on || !g->coef || !g->coef->sigma_on) return te::fail(TE_ESTATE, "te_gmg_reaction: no reaction term is set");
+		if ((rc = checkLevelVec(g, level, out, "te_gmg_reaction"))) return rc;
+		if (out->n) HIPCHK(hipMemcpyAsync(out->d, g->coef->sigma[level]->d, sizeof(double) * out->n, hipMemcpyDeviceToDevice, g->stream));
 		return TE_OK;
 	});
 }

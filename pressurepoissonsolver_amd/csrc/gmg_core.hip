@@ -593,7 +593,7 @@ int te_gmg_release_workspace(te_gmg *g)
 				v = nullptr;
 			}
 			fmgFree(g);
-			if (!g->coef_on) coefFree(g); // (a coefficient that is set stays: the solver's operator depends on it)
+			coefRelease(g); // (a coefficient or a reaction term that is set stays: the solver's operator depends on it)
 			return TE_OK;
 	});
 }

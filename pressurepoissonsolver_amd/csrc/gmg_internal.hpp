@@ -432,7 +432,8 @@ struct te_gmg {
 	struct SchurWs *schur = nullptr;  // the Schur route's device tables and work vectors (gmg_schur.hip), made at its first use
 	struct RegridWs *regrid = nullptr; // the indicator's device output and the transfer's map (gmg_regrid.hip), made at their first use
 	// te_gmg_set_coefficient (gmg_coef.hip): the solver's own copy of beta on every level, made at the first call and kept; coef_on:
-	// a coefficient is set -- te_apply, te_residual, te_smooth, te_vcycle and te_bicgstab take the variable-coefficient path
+	// a coefficient is set -- te_apply, te_residual, te_smooth, te_vcycle and te_bicgstab take the variable-coefficient path.
+	// te_gmg_set_reaction's per-level sigma and its flag live in CoefWs as well (the term exists on that path only).
 	struct CoefWs *coef = nullptr;
 	bool           coef_on = false;
 	// level 0 = the leaves of the mesh: tree node id, tree parent, orthant there, lower corner and lengths per patch (host copies of
@@ -753,7 +754,8 @@ void fmgFree(te_gmg *g); // (te_gmg_release_workspace, te_gmg_destroy)
 void regridFree(te_gmg *g); // (te_gmg_destroy)
 int  regridMapUpload(te_gmg *src, te_gmg *dst, const char *who, const int32_t **map_dev); // one row per patch of dst, in dst's buffer
 // ---- gmg_coef.hip (with a coefficient set: the operator A_b = div(beta grad .) in place of the Laplacian)
-void coefFree(te_gmg *g); // (te_gmg_destroy; te_gmg_release_workspace while no coefficient is set)
+void coefFree(te_gmg *g);    // (te_gmg_destroy)
+void coefRelease(te_gmg *g); // (te_gmg_release_workspace: coefFree while no coefficient is set, else the sigma buffers while sigma is cleared)
 int  coefStencil(te_gmg *g, LevelHost &L, int mode, const double *u, const double *f, double *out, double omega); // mode: coefkernels.hpp CoefMode
 int  coefSmoothOnce(te_gmg *g, int level, const te_vec *f, te_vec *u, int smoother, double omega);
 int  vcycleCoef(te_gmg *g, const te_cycle_opts *o, const te_vec *f, te_vec *u); // te_vcycle with a coefficient (visitCoef)
