@@ -678,6 +678,45 @@ int te_gmg_set_reaction(te_gmg *g, const te_vec *sigma);
 int te_gmg_has_reaction(const te_gmg *g);
 int te_gmg_reaction(te_gmg *g, int level, te_vec *out);
 
+/* The coarsest level of the variable-coefficient cycle. By default te_vcycle with a coefficient runs
+ * coarse_sweeps sweeps there (TE_COEF_COARSE_SWEEPS). With TE_COEF_COARSE_SUBCYCLE a coarsest level of ONE patch of n^D cells is solved
+ * by multigrid again: it is the same grid as a uniform tree of (n / sub_n)^D patches of sub_n^D cells, on which the path's own kernels
+ * and its own coarse levels exist. In place of the coarse_sweeps loop:
+ *   1. f and the incoming u of the one-patch level are split into the level-0 vectors of an AUXILIARY solver on a root of the same
+ *      lengths and per-side boundary kinds, log2(n / sub_n) uniform refinements, patch size sub_n;
+ *   2. that solver's cycle (the driver above, u carried, not zeroed) runs `cycles` times with the caller's te_cycle_opts -- smoother,
+ *      pre / mid / post sweeps, cycle type, omega, and coarse_sweeps, which now counts sweeps on the one sub_n^D patch -- and the
+ *      parent's interpolator at that moment;
+ *   3. u is merged back.
+ * The auxiliary level-0 beta and sigma are the split of the parent's coarsest-level beta and sigma: a patch's LO block is the matching
+ * block of the big patch's LO; its HI is the big LO plane at offset + sub_n, or the big HI on the big patch's upper face (the two
+ * copies of a shared face are equal by construction). Below that the auxiliary solver restricts as te_gmg_set_coefficient /
+ * te_gmg_set_reaction do. Every te_gmg_set_coefficient and te_gmg_set_reaction of the parent refreshes them, and so does
+ * te_gmg_set_coef_coarse itself when a coefficient is set; "beta first, then sigma; every beta clears sigma" holds for both solvers.
+ *
+ * The setting is a property of the SOLVER, not of a coefficient: it may be made with or without beta set and survives every
+ * te_gmg_set_coefficient, NULL included. The default is TE_COEF_COARSE_SWEEPS; until the call is made nothing changes. te_smooth on
+ * the coarsest level is untouched. A hierarchy of one level is allowed (te_vcycle is then the sub-solve alone). No silent fallback:
+ * what te_gmg_coef_coarse reports is what runs.
+ *
+ * sub_n is valid if it is even, >= 4, in 3D one of 4, 8, 16, and n / sub_n is a power of two >= 2. sub_n = 0 picks one: in 3D 8 where
+ * that is valid (the measured choice: DESIGN.md section 20), otherwise the smallest valid value, which is 4 where 4 is valid.
+ * te_gmg_set_coef_coarse returns
+ *   TE_EINVAL        unknown kind, cycles < 1, an invalid explicit sub_n;
+ *   TE_ESTATE        a sharded hierarchy (the message says "sharded");
+ *   TE_EUNSUPPORTED  the coarsest level has more than one patch (a truncated hierarchy; the message carries the count), or no valid
+ *                    sub_n exists (n = 4 in 3D; in 2D an n whose halves never reach an even size >= 4, e.g. no multiple of 4);
+ * and changes nothing then. With TE_COEF_COARSE_SWEEPS only kind and cycles are checked (sub_n is not used).
+ * The auxiliary mesh, hierarchy and solver belong to the parent: made by the first TE_COEF_COARSE_SUBCYCLE call (again when sub_n
+ * changes), on the parent's stream; te_gmg_release_workspace frees them while the kind is TE_COEF_COARSE_SWEEPS, te_gmg_destroy always.
+ * te_gmg_profile and its companions act on the auxiliary solver too; its launches are counted in the parent's rows under their
+ * existing names, the split and the merge as "coef_split" and "coef_merge".
+ * te_gmg_coef_coarse: the current kind, the RESOLVED sub_n (0 while no sub-cycle has been selected) and cycles; NULL outputs are skipped. */
+#define TE_COEF_COARSE_SWEEPS   0 /* default: coarse_sweeps sweeps on the coarsest level */
+#define TE_COEF_COARSE_SUBCYCLE 1
+int te_gmg_set_coef_coarse(te_gmg *g, int kind, int sub_n, int cycles);
+int te_gmg_coef_coarse(const te_gmg *g, int *kind, int *sub_n, int *cycles);
+
 /* kernel timing hooks for bench.py: HIP-event time of the last te_vcycle's dominant kernel */
 int te_gmg_profile(te_gmg *g, int enable);
 /* name[i] (<=63 chars), calls[i], total_ms[i] (HIP events on the solver stream), cells[i]

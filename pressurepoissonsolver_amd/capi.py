@@ -32,6 +32,7 @@ PROBLEM_TRIG, PROBLEM_GAUSS, PROBLEM_RANDOM = 0, 1, 2
 SCHUR_PREC_NONE, SCHUR_PREC_CHEB = 0, 1
 INTERP_DIRECT, INTERP_LINEAR = 0, 1  # TE_INTERP_*: DrctIntp (the default), tri-/bilinear
 SLABS_STENCIL, SLABS_SWEEP = 0, 1  # TE_SLABS_*: which slab rule te_gmg_slab_count reports
+COEF_COARSE_SWEEPS, COEF_COARSE_SUBCYCLE = 0, 1  # TE_COEF_COARSE_*: the coarsest level of the cycle with a coefficient
 
 
 class CycleOpts(C.Structure):
@@ -181,6 +182,8 @@ SYMBOLS = {
     "te_gmg_set_reaction": (_I, [_P, _P]),
     "te_gmg_has_reaction": (_I, [_P]),
     "te_gmg_reaction": (_I, [_P, _I, _P]),
+    "te_gmg_set_coef_coarse": (_I, [_P, _I, _I, _I]),
+    "te_gmg_coef_coarse": (_I, [_P, C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)]),
     "te_integrate": (_I, [_P, _I, _P, _P]),
     "te_volume": (_I, [_P, _I, _P]),
 }
@@ -627,6 +630,18 @@ class GMG:
     def reaction(self, level, out):
         """out (a cell vector of `level`) = the solver's sigma on that level"""
         check(lib().te_gmg_reaction(self.h, level, out.h))
+
+    # ---- the coarsest level of the cycle with a coefficient (te_hip.h te_gmg_set_coef_coarse): a property of the solver
+    def set_coef_coarse(self, kind, sub_n=0, cycles=2):
+        """COEF_COARSE_SWEEPS (default: coarse_sweeps sweeps) or COEF_COARSE_SUBCYCLE: a one-patch coarsest level is split into
+        patches of sub_n cells per axis (0: in 3D 8 where valid, else the smallest valid size) and solved by `cycles` cycles of an auxiliary solver"""
+        check(lib().te_gmg_set_coef_coarse(self.h, int(kind), int(sub_n), int(cycles)))
+
+    def coef_coarse(self):
+        """-> (kind, resolved sub_n, cycles)"""
+        k, s, c = C.c_int(), C.c_int(), C.c_int()
+        check(lib().te_gmg_coef_coarse(self.h, C.byref(k), C.byref(s), C.byref(c)))
+        return k.value, s.value, c.value
 
     def faces_restrict(self, fine_level, fine, coarse):
         """coarse (a face vector of fine_level + 1) = the face average of fine"""

@@ -7,12 +7,6 @@
 #include "gmg_ghosts3d.hpp"
 #include "coefkernels.hpp" // (with faceregridkernels.hpp: the LAST include, FMA contraction is off from there on)
 
-struct CoefWs {
-	std::vector<te_vec *> beta;  // [level] face vectors of the solver
-	std::vector<te_vec *> sigma; // [level] cell vectors of the solver: the reaction term (te_gmg_set_reaction); empty until the first call
-	bool                  sigma_on = false; // the operator is A_b,sigma = A_b - sigma
-};
-
 namespace tei
 {
 static void sigmaFree(CoefWs *W)
@@ -230,8 +224,9 @@ int coefSmoothOnce(te_gmg *g, int level, const te_vec *f, te_vec *u, int smoothe
 }
 
 // GMG/Cycle.h:56-126 with VCycle.h:44-62 / WCycle.h:45-68, statement for statement, on A_b: no fused form, no exact coarse solve
-// (the coarsest level runs coarse_sweeps sweeps of o->smoother). The transfers are the constant-coefficient cycle's own.
-static int visitCoef(te_gmg *g, const te_cycle_opts *o, int l, const te_vec *f, te_vec *u)
+// (the coarsest level runs coarse_sweeps sweeps of o->smoother, or with TE_COEF_COARSE_SUBCYCLE the sub-patch cycles of
+// gmg_coefcoarse.hip). The transfers are the constant-coefficient cycle's own.
+int visitCoef(te_gmg *g, const te_cycle_opts *o, int l, const te_vec *f, te_vec *u)
 {
 	const int  nl = (int) g->levels.size();
 	LevelHost &L  = *g->levels[l];
@@ -242,7 +237,7 @@ static int visitCoef(te_gmg *g, const te_cycle_opts *o, int l, const te_vec *f, 
 			if (int r = coefSmoothOnce(g, l, f, u, o->smoother, o->omega)) return r;
 		return TE_OK;
 	};
-	if (l == nl - 1) return smooth(o->coarse_sweeps);
+	if (l == nl - 1) return g->cc_kind == TE_COEF_COARSE_SUBCYCLE ? coefCoarseSolve(g, o, f, u) : smooth(o->coarse_sweeps);
 	LevelHost &C = *g->levels[l + 1];
 	auto descend = [&]() -> int {
 		int r;
@@ -297,7 +292,7 @@ int te_gmg_set_coefficient(te_gmg *g, const te_vec *beta)
 		if (g->coef) g->coef->sigma_on = false; // every call clears sigma: never a new beta with a stale sigma (the order per step is beta, then sigma)
 		if (!beta) { // (also on a sharded hierarchy, where none can be set: nothing to clear)
 			g->coef_on = false;
-			return TE_OK;
+			return coefCoarseRefresh(g, true);
 		}
 		if ((rc = refuseSharded(g, "te_gmg_set_coefficient"))) return rc;
 		if ((rc = checkFaces(g, 0, beta, "te_gmg_set_coefficient"))) return rc;
@@ -318,7 +313,8 @@ int te_gmg_set_coefficient(te_gmg *g, const te_vec *beta)
 		for (int l = 0; l + 1 < nl; l++)
 			if ((rc = facesRestrict(g, l, B[l]->d, B[l + 1]->d))) return rc;
 		g->coef_on = true;
-		return TE_OK;
+		if ((rc = coefCoarseRefresh(g, true))) g->coef_on = false; // (the sub-patch coarse solve's copies: never a stale one)
+		return rc;
 	});
 }
 
@@ -347,7 +343,7 @@ int te_gmg_set_reaction(te_gmg *g, const te_vec *sigma)
 		for (auto &L : g->levels) L->xf_valid_for = nullptr; // (the operator changes)
 		if (!sigma) { // (also where none can be set: nothing to clear)
 			if (g->coef) g->coef->sigma_on = false;
-			return TE_OK;
+			return coefCoarseRefresh(g, false);
 		}
 		if ((rc = refuseSharded(g, "te_gmg_set_reaction"))) return rc;
 		if (!g->coef_on || !g->coef)
@@ -370,7 +366,8 @@ int te_gmg_set_reaction(te_gmg *g, const te_vec *sigma)
 		for (int l = 0; l + 1 < nl; l++)
 			if ((rc = doRestrict(g, l, S[l]->d, S[l + 1]->d))) return rc; // te_restrict's average; copy-through patches bit for bit
 		g->coef->sigma_on = true;
-		return TE_OK;
+		if ((rc = coefCoarseRefresh(g, false))) g->coef->sigma_on = false;
+		return rc;
 	});
 }
 

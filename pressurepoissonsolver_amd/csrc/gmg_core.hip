@@ -11,7 +11,8 @@ const char *kclassName[KC_COUNT] = {"stencil_apply", "stencil_resid", "stencil_j
                                     "rbgs_resweep_prolong_fcorr", "rbgs_zero_resid_restrict_faces_fcorr", "fcorr_gather", "patch_solve_mfma_faces",
                                     "bicg_update", "bicg_s", "bicg_p", "stencil_apply_dot", "patch_bcgs", "gradient", "divergence", "project", "prolong_linear", "prolong_quadratic", "boundary_restrict",
                                     "indicator", "regrid", "regrid_faces",
-                                    "apply_coef", "resid_coef", "jacobi_coef", "rbgs_coef", "faces_restrict"};
+                                    "apply_coef", "resid_coef", "jacobi_coef", "rbgs_coef", "faces_restrict",
+                                    "coef_split", "coef_merge"};
 const char *optName[O_COUNT] = {"TE_2D_SIMPLE", "TE_2D_NO_MFMA", "TE_2D_NO_PF", "TE_2D_NO_MR_FUSE", "TE_2D_TPB", "TE_NO_FUSE2", "TE_NO_FUSE3",
                                 "TE_NO_FUSE3_CF", "TE_NO_CFP", "TE_NO_XF", "TE_NO_FCORR", "TE_NO_FCORR_CF", "TE_NO_OVERLAP",
                                 "TE_OVERLAP_MIN", "TE_NO_PS_FACES", "TE_PS_MODE", "TE_PS_SLOW", "TE_RBGS_NOSLAB", "TE_ZS_FORCE", "TE_NO_ZS8",
@@ -161,6 +162,14 @@ void te_cycle_opts_default(te_cycle_opts *o)
 
 int te_gmg_create(const te_hier *h, int device, te_gmg **out)
 {
+	return guarded([&]() -> int { return tei::gmgCreate(h, device, nullptr, out); });
+}
+} // extern "C"
+
+namespace tei
+{
+int gmgCreate(const te_hier *h, int device, hipStream_t borrowed, te_gmg **out)
+{
 	return guarded([&]() -> int {
 		if (!h || !out) return te::fail(TE_EINVAL, "te_gmg_create: null argument");
 		using clk = std::chrono::steady_clock;
@@ -187,6 +196,8 @@ int te_gmg_create(const te_hier *h, int device, te_gmg **out)
 		g->placement[4] = (double) h->h.neumann_sides;
 		g->leaf_id = h->h.leaf_id, g->leaf_parent = h->h.leaf_parent, g->leaf_orth = h->h.leaf_orth;
 		g->leaf_starts = h->h.levels[0].g_starts, g->leaf_lengths = h->h.levels[0].g_lengths;
+		g->coarse_P_global = h->h.levels.back().P_global;
+		g->coarse_starts = h->h.levels.back().g_starts, g->coarse_lengths = h->h.levels.back().g_lengths;
 		memset(g->calls, 0, sizeof(g->calls));
 		memset(g->cells, 0, sizeof(g->cells));
 		memset(g->total_ms, 0, sizeof(g->total_ms));
@@ -195,7 +206,10 @@ int te_gmg_create(const te_hier *h, int device, te_gmg **out)
 			return te::fail(TE_EINVAL, "te_gmg_create: TE_ZS_PIN must be 1, 2, 4 or 8");
 		if (g->cfg.has(O_RESWEEP_V) && !(g->resweep_pin = parseResweepPin(g->cfg.str(O_RESWEEP_V))))
 			return te::fail(TE_EINVAL, "te_gmg_create: TE_RESWEEP_V must be 19, 27 or 59");
-		HIPCHK(hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking));
+		if (borrowed)
+			g->stream = borrowed, g->stream_borrowed = true;
+		else
+			HIPCHK(hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking));
 		HIPCHK(hipStreamCreateWithFlags(&g->comm_stream, hipStreamNonBlocking));
 		HIPCHK(hipEventCreateWithFlags(&g->ev_pack, hipEventDisableTiming));
 		HIPCHK(hipEventCreateWithFlags(&g->ev_recv, hipEventDisableTiming));
@@ -248,7 +262,9 @@ int te_gmg_create(const te_hier *h, int device, te_gmg **out)
 		return TE_OK;
 	});
 }
+} // namespace tei
 
+extern "C" {
 int te_gmg_setup_ms(const te_gmg *g, double *out, int n)
 {
 	return guarded([&]() -> int {
@@ -274,6 +290,7 @@ void te_gmg_destroy(te_gmg *g)
 	fmgFree(g);
 	schurFree(g);
 	regridFree(g);
+	coefCoarseFree(g); // (the auxiliary solver runs on this solver's stream: it goes first)
 	coefFree(g);
 	for (auto &e : g->ev_pool) {
 		(void) hipEventDestroy(e.a);
@@ -284,7 +301,7 @@ void te_gmg_destroy(te_gmg *g)
 	if (g->ev_pack) (void) hipEventDestroy(g->ev_pack);
 	if (g->ev_recv) (void) hipEventDestroy(g->ev_recv);
 	if (g->comm_stream) (void) hipStreamDestroy(g->comm_stream);
-	(void) hipStreamDestroy(g->stream);
+	if (!g->stream_borrowed) (void) hipStreamDestroy(g->stream);
 	delete g;
 }
 
@@ -450,6 +467,7 @@ int te_gmg_profile(te_gmg *g, int enable)
 		if (!g) return te::fail(TE_EINVAL, "te_gmg_profile: null");
 		drainEvents(g);
 		g->profiling = enable != 0;
+		if (g->cc_aux) return te_gmg_profile(g->cc_aux, enable); // (the sub-patch coarse solve's launches are part of this solver's cycle)
 		return TE_OK;
 	});
 }
@@ -495,10 +513,12 @@ int te_gmg_profile_select(te_gmg *g, const char *name)
 		if (!g) return te::fail(TE_EINVAL, "te_gmg_profile_select: null");
 		drainEvents(g);
 		g->prof_only = -1;
+		if (g->cc_aux) drainEvents(g->cc_aux), g->cc_aux->prof_only = -1;
 		if (!name || !*name) return TE_OK;
 		for (int k = 0; k < KC_COUNT; k++)
 			if (!strcmp(name, kclassName[k])) {
 				g->prof_only = k;
+				if (g->cc_aux) g->cc_aux->prof_only = k;
 				return TE_OK;
 			}
 		return te::fail(TE_EINVAL, std::string("te_gmg_profile_select: unknown kernel class ") + name);
@@ -512,6 +532,7 @@ int te_gmg_profile_stride(te_gmg *g, int stride)
 		drainEvents(g);
 		g->prof_stride = stride > 1 ? stride : 1;
 		memset(g->prof_seq, 0, sizeof(g->prof_seq));
+		if (g->cc_aux) return te_gmg_profile_stride(g->cc_aux, stride);
 		return TE_OK;
 	});
 }
@@ -524,6 +545,7 @@ int te_gmg_profile_reset(te_gmg *g)
 		memset(g->calls, 0, sizeof(g->calls));
 		memset(g->cells, 0, sizeof(g->cells));
 		memset(g->total_ms, 0, sizeof(g->total_ms));
+		if (g->cc_aux) return te_gmg_profile_reset(g->cc_aux);
 		return TE_OK;
 	});
 }
@@ -534,14 +556,16 @@ int te_gmg_profile_rows(te_gmg *g, int max_rows, char (*name)[64], int64_t *call
 	return guarded([&]() -> int {
 		if (!g || !name || !calls || !total_ms || !cells) return te::fail(TE_EINVAL, "te_gmg_profile_rows: null");
 		drainEvents(g);
+		const te_gmg *x = g->cc_aux; // the auxiliary solver of the sub-patch coarse solve: its launches count under their own class names
+		if (x) drainEvents(g->cc_aux);
 		int n = 0;
 		for (int k = 0; k < KC_COUNT && n < max_rows; k++) {
-			if (g->calls[k] == 0) continue;
+			if (g->calls[k] + (x ? x->calls[k] : 0) == 0) continue;
 			strncpy(name[n], kclassName[k], 63);
 			name[n][63] = 0;
-			calls[n]    = g->calls[k];
-			total_ms[n] = g->total_ms[k];
-			cells[n]    = g->cells[k];
+			calls[n]    = g->calls[k] + (x ? x->calls[k] : 0);
+			total_ms[n] = g->total_ms[k] + (x ? x->total_ms[k] : 0.0);
+			cells[n]    = g->cells[k] + (x ? x->cells[k] : 0);
 			n++;
 		}
 		return n;
@@ -594,6 +618,7 @@ int te_gmg_release_workspace(te_gmg *g)
 			}
 			fmgFree(g);
 			coefRelease(g); // (a coefficient or a reaction term that is set stays: the solver's operator depends on it)
+			coefCoarseRelease(g); // (the auxiliary solver goes while the kind is TE_COEF_COARSE_SWEEPS, else it stays)
 			return TE_OK;
 	});
 }
@@ -620,6 +645,7 @@ int te_gmg_set_option(te_gmg *g, const char *name, const char *value)
 						g->resweep_pin = pin;
 					}
 					g->cfg.set(o, value);
+					if (g->cc_aux) (void) te_gmg_set_option(g->cc_aux, name, value); // (the auxiliary solver picks its kernels by the same switches)
 					if (o == O_PUSH_TIMEOUT) g->push.timeout_s = value ? std::max(0.1, atof(value)) : (g->wd.timeout_s > 0 ? g->wd.timeout_s : 300.0);
 					g->verified_opts.clear(); // (an option may change which exchanges a cycle issues)
 					return TE_OK;

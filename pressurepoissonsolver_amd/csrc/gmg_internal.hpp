@@ -16,6 +16,7 @@
 //   gmg_regrid.hip     the per-patch indicator te_patch_indicator and the transfer between two meshes te_vec_regrid (regridkernels.hpp)
 //   gmg_faceregrid.hip the transfer of a face vector between two meshes te_faces_regrid (faceregridkernels.hpp)
 //   gmg_coef.hip       the variable-coefficient operator div(beta grad u): coefficient per level, operator, sweeps, cycle (coefkernels.hpp)
+//   gmg_coefcoarse.hip its sub-patch coarse solve te_gmg_set_coef_coarse: the auxiliary solver on the split tree (coefcoarsekernels.hpp)
 #pragma once
 #include "capi_common.hpp"
 #include "dispatch.hpp"
@@ -70,6 +71,12 @@ struct te_vec {
 	bool    faces = false; // a face vector of the level (te_vec_create_faces): per local patch dim n^dim + dim n^(dim-1) doubles
 };
 
+struct CoefWs { // te_gmg::coef (gmg_coef.hip)
+	std::vector<te_vec *> beta;  // [level] face vectors of the solver
+	std::vector<te_vec *> sigma; // [level] cell vectors of the solver: the reaction term (te_gmg_set_reaction); empty until the first call
+	bool                  sigma_on = false; // the operator is A_b,sigma = A_b - sigma
+};
+
 namespace tei
 {
 enum KClass : int {
@@ -103,7 +110,9 @@ enum KClass : int {
 	KC_FACE_REGRID,
 	// the variable-coefficient path (coefkernels.hpp): operator, residual, Jacobi, one RB-GS sweep (both colour launches), and the
 	// restriction of the coefficient (cells = coarse sites)
-	KC_APPLY_COEF, KC_RESID_COEF, KC_JACOBI_COEF, KC_RBGS_COEF, KC_FACES_RESTRICT, KC_COUNT
+	KC_APPLY_COEF, KC_RESID_COEF, KC_JACOBI_COEF, KC_RBGS_COEF, KC_FACES_RESTRICT,
+	// the sub-patch coarse solve (coefcoarsekernels.hpp): one-patch level -> auxiliary level 0 (cells = doubles moved) and back
+	KC_COEF_SPLIT, KC_COEF_MERGE, KC_COUNT
 };
 extern const char *kclassName[KC_COUNT]; // (gmg_core.hip)
 
@@ -403,6 +412,7 @@ struct te_gmg {
 	int                                     resweep_pin = 0; // TE_RESWEEP_V likewise (dispatch.hpp resweepVariant)
 	int                                     device = 0;
 	hipStream_t                             stream = nullptr;
+	bool                                    stream_borrowed = false; // an auxiliary solver (gmgCreate with a stream): runs on its owner's stream, never destroys it
 	// ghost exchanges run on their own stream so that interior patches compute underneath them
 	hipStream_t comm_stream = nullptr;
 	hipEvent_t  ev_pack = nullptr, ev_recv = nullptr;
@@ -436,6 +446,15 @@ struct te_gmg {
 	// te_gmg_set_reaction's per-level sigma and its flag live in CoefWs as well (the term exists on that path only).
 	struct CoefWs *coef = nullptr;
 	bool           coef_on = false;
+	// te_gmg_set_coef_coarse (gmg_coefcoarse.hip): how visitCoef treats its coarsest level. A property of the solver, not of a
+	// coefficient: it survives te_gmg_set_coefficient. cc: the auxiliary mesh's solver on the split tree, its vectors and the offset
+	// table, made by the first SUBCYCLE call; cc_aux = cc's solver (what the profile calls and te_gmg_set_option pass on to).
+	int                   cc_kind = 0 /* TE_COEF_COARSE_SWEEPS */, cc_sub_n = 0, cc_cycles = 2;
+	struct CoefCoarseWs  *cc = nullptr;
+	te_gmg               *cc_aux = nullptr;
+	// the coarsest level's patches as the hierarchy had them (host, global order): the auxiliary root takes the one patch's box
+	int                  coarse_P_global = 0;
+	std::vector<double>  coarse_starts, coarse_lengths;
 	// level 0 = the leaves of the mesh: tree node id, tree parent, orthant there, lower corner and lengths per patch (host copies of
 	// the hierarchy's te_hier_leaf_tree / level tables, global order): what te_vec_regrid matches two meshes by
 	std::vector<int32_t> leaf_id, leaf_parent, leaf_orth;
@@ -753,12 +772,22 @@ void fmgFree(te_gmg *g); // (te_gmg_release_workspace, te_gmg_destroy)
 // ---- gmg_regrid.hip
 void regridFree(te_gmg *g); // (te_gmg_destroy)
 int  regridMapUpload(te_gmg *src, te_gmg *dst, const char *who, const int32_t **map_dev); // one row per patch of dst, in dst's buffer
+// ---- gmg_core.hip
+// te_gmg_create; stream != null: the new solver runs on that stream and never destroys it (the auxiliary solver of gmg_coefcoarse.hip)
+int gmgCreate(const te_hier *h, int device, hipStream_t stream, te_gmg **out);
 // ---- gmg_coef.hip (with a coefficient set: the operator A_b = div(beta grad .) in place of the Laplacian)
 void coefFree(te_gmg *g);    // (te_gmg_destroy)
 void coefRelease(te_gmg *g); // (te_gmg_release_workspace: coefFree while no coefficient is set, else the sigma buffers while sigma is cleared)
 int  coefStencil(te_gmg *g, LevelHost &L, int mode, const double *u, const double *f, double *out, double omega); // mode: coefkernels.hpp CoefMode
 int  coefSmoothOnce(te_gmg *g, int level, const te_vec *f, te_vec *u, int smoother, double omega);
 int  vcycleCoef(te_gmg *g, const te_cycle_opts *o, const te_vec *f, te_vec *u); // te_vcycle with a coefficient (visitCoef)
+int  visitCoef(te_gmg *g, const te_cycle_opts *o, int l, const te_vec *f, te_vec *u); // the cycle from level l on, u carried
+// ---- gmg_coefcoarse.hip (te_gmg_set_coef_coarse: the coarsest level of visitCoef solved by cycles on the split tree)
+void coefCoarseFree(te_gmg *g);    // (te_gmg_destroy: before the stream goes)
+void coefCoarseRelease(te_gmg *g); // (te_gmg_release_workspace: coefCoarseFree while the kind is TE_COEF_COARSE_SWEEPS)
+// the auxiliary solver's beta (with_beta) and sigma from the parent's coarsest level, or cleared as the parent's are
+int  coefCoarseRefresh(te_gmg *g, bool with_beta);
+int  coefCoarseSolve(te_gmg *g, const te_cycle_opts *o, const te_vec *f, te_vec *u); // in place of the coarse_sweeps loop
 // the calls that have no variable-coefficient form: TE_ESTATE while one is set
 inline int coefRefuse(const te_gmg *g, const char *who)
 {

@@ -64,6 +64,12 @@ Tree Tree::read(const std::string &path, int dim)
 
 Tree Tree::unitRoot(int dim)
 {
+	const double starts[MAX_D] = {0.0, 0.0, 0.0}, lengths[MAX_D] = {1.0, 1.0, 1.0};
+	return boxRoot(dim, starts, lengths);
+}
+
+Tree Tree::boxRoot(int dim, const double *starts, const double *lengths)
+{
 	Tree t;
 	t.dim = dim;
 	Node nd;
@@ -71,8 +77,8 @@ Tree Tree::unitRoot(int dim)
 	nd.level  = 1;
 	nd.parent = -1;
 	for (int i = 0; i < dim; i++) {
-		nd.lengths[i] = 1.0;
-		nd.starts[i]  = 0.0;
+		nd.lengths[i] = lengths[i];
+		nd.starts[i]  = starts[i];
 	}
 	t.nodes[0]   = nd;
 	t.root       = 0;

@@ -51,6 +51,9 @@ struct Tree {
 	static Tree read(const std::string &path, int dim);
 	/// single root node on the unit box, level 1 (what a 1-node mesh file holds)
 	static Tree unitRoot(int dim);
+	/// the same on the box [starts, starts + lengths): the auxiliary tree of the sub-patch coarse solve (gmg_coefcoarse.hip); no
+	/// public mesh call makes one
+	static Tree boxRoot(int dim, const double *starts, const double *lengths);
 	/// split every leaf once; new ids are ++max_id in (depth, id) leaf order then orthant
 	/// order, as OctTree.h:119-179 + :183-189 assign them.
 	void refineLeaves();
