@@ -635,7 +635,8 @@ int te_project(te_gmg *g, int level, double alpha, const te_vec *p, const te_vec
  *   contains "coefficient".
  *   te_gradient, te_divergence, te_project, te_restrict, the prolongations, the BLAS-1 calls, the boundary and the regrid calls never
  *   involve beta and are unchanged. te_add_boundary_rhs folds the CONSTANT-coefficient terms: with a coefficient the right-hand-side
- *   terms of boundary data are -te_divergence(1, beta (.) te_gradient(0, bdata)).
+ *   terms of boundary data are -te_divergence(1, beta (.) te_gradient(0, bdata)), or in one call
+ *   te_add_boundary_rhs_weighted(bdata, beta, .) below.
  *
  * Every call of te_gmg_set_coefficient, with beta or with NULL, CLEARS the reaction term sigma (te_gmg_set_reaction below): the order
  * per time step is beta, then sigma. */
@@ -716,6 +717,52 @@ int te_gmg_reaction(te_gmg *g, int level, te_vec *out);
 #define TE_COEF_COARSE_SUBCYCLE 1
 int te_gmg_set_coef_coarse(te_gmg *g, int kind, int sub_n, int cycles);
 int te_gmg_coef_coarse(const te_gmg *g, int *kind, int *sub_n, int *cycles);
+
+/* A variable-density projection step on the device: rho (or mu) stays a CELL vector, the face coefficient is built from it here, the
+ * boundary terms of the right-hand side are folded under it, and the velocity correction u = u* - dt beta grad p is one pass. All three
+ * calls are additive: none reads or changes the coefficient of te_gmg_set_coefficient, and a te_vcycle afterwards gives the bits it
+ * gave before.
+ *
+ * te_faces_from_cells(g, level, mode, c, cb, F): c = a domain vector of `level`, cb = a boundary vector of `level` or NULL, F = a face
+ * vector of `level`. Every LO_a / HI_a entry of every patch is written by exactly one writer, no atomics. A face has two operands: lo,
+ * the value on its lower-coordinate side, and hi, the value on its upper side.
+ *   TE_FACE_MEAN        (lo + hi) * 0.5                 (a viscosity)
+ *   TE_FACE_HARMONIC    (2.0 * (lo * hi)) / (lo + hi)
+ *   TE_FACE_RECIP_MEAN  2.0 / (lo + hi)                 (beta = 1 / rho_face)
+ *   interior face, patch face with a same-level neighbour: the two adjacent cells, the neighbour's read in place; both stored copies of
+ *     such a face receive the same bits in every mode.
+ *   physical face (Dirichlet and Neumann alike: the coefficient field has no boundary condition of its own): v = cb's entry for that face
+ *     point where cb is given, else the cell just inside; the result is v bit for bit (MEAN, HARMONIC) or 1.0 / v (RECIP_MEAN).
+ *   coarse/fine face: plain averages, not the operator's ghost 2 gamma - m (gamma carries weights of -1/12 and can go negative across a
+ *     jump). Fine side: the other operand is the coarse neighbour's cell of its facing layer that covers the face, at
+ *     ((a + (q & 1 ? n : 0)) / 2, (b + (q & 2 ? n : 0)) / 2), q = this patch's quadrant on the coarse face. Coarse side: the other operand is
+ *     ((f00 + f10) + (f01 + f11)) * 0.25 over the four fine cells of the facing layer that cover the coarse cell, first index along the
+ *     face's lower remaining axis (2D: (f0 + f1) * 0.5). The two copies differ by construction, as for te_gradient; in MEAN mode the coarse
+ *     copy equals the mean of the four fine copies up to rounding.
+ * All operands must be > 0 for the two division modes; nothing checks this, exactly as for beta. Works on every level.
+ * ORDER OF ACCURACY. Without cb the coefficient on a physical face is the inner cell's value, an O(h) error there. That is harmless where
+ * the flux datum on that face is zero (walls) or the face is Dirichlet (the solve stays second order), and FIRST order where an
+ * inhomogeneous Neumann datum g_n != 0 meets it: pass the wall values of the field in cb then (second order again).
+ * TE_EINVAL: NULL (c, F), a vector of the wrong kind, level or solver, an unknown mode. TE_ESTATE (the message says "sharded") on a
+ * sharded hierarchy.
+ *
+ * te_project_weighted(g, level, alpha, p, bdata, w, U): U <- U - alpha (w (.) grad p) in one pass, the gradient never stored. G is
+ * exactly te_gradient(p, bdata)'s value (the same ghosts; on a physical Neumann face g_n itself); t = w * G is one multiplication, then
+ * U = fma(-alpha, t, U). With w = 1 everywhere the call gives te_project's bits; both copies of a same-level face get the same bits when
+ * w's (and U's) copies agree. w = a face vector of the level, distinct from U. TE_EINVAL: w aliases U, wrong kinds, levels or solvers.
+ * TE_ESTATE ("sharded") on a sharded hierarchy.
+ *
+ * te_add_boundary_rhs_weighted(g, level, bdata, w, f): te_add_boundary_rhs with every datum multiplied first by w on its physical face,
+ * b <- w_face * b (w_face = LO_a of the layer's cell on a lower side, HI_a on an upper side), then the same expressions: Dirichlet
+ * f -= 2 b / (h h), Neumann f += b / h below, f -= b / h above; the same owner rule, side order and one writer per cell. With w = 1 the
+ * bits of te_add_boundary_rhs; up to rounding -te_divergence(1, w (.) te_gradient(0, bdata)), the boundary terms under A_b with
+ * beta = w. Patch-local: runs on a sharded hierarchy like te_add_boundary_rhs. TE_EINVAL: wrong kinds, levels or solvers. */
+#define TE_FACE_MEAN       0
+#define TE_FACE_HARMONIC   1
+#define TE_FACE_RECIP_MEAN 2
+int te_faces_from_cells(te_gmg *g, int level, int mode, const te_vec *c, const te_vec *cb, te_vec *F);
+int te_project_weighted(te_gmg *g, int level, double alpha, const te_vec *p, const te_vec *bdata, const te_vec *w, te_vec *U);
+int te_add_boundary_rhs_weighted(te_gmg *g, int level, const te_vec *bdata, const te_vec *w, te_vec *f);
 
 /* kernel timing hooks for bench.py: HIP-event time of the last te_vcycle's dominant kernel */
 int te_gmg_profile(te_gmg *g, int enable);

@@ -32,6 +32,7 @@ PROBLEM_TRIG, PROBLEM_GAUSS, PROBLEM_RANDOM = 0, 1, 2
 SCHUR_PREC_NONE, SCHUR_PREC_CHEB = 0, 1
 INTERP_DIRECT, INTERP_LINEAR = 0, 1  # TE_INTERP_*: DrctIntp (the default), tri-/bilinear
 SLABS_STENCIL, SLABS_SWEEP = 0, 1  # TE_SLABS_*: which slab rule te_gmg_slab_count reports
+FACE_MEAN, FACE_HARMONIC, FACE_RECIP_MEAN = 0, 1, 2  # TE_FACE_*: how te_faces_from_cells combines the two operands of a face
 COEF_COARSE_SWEEPS, COEF_COARSE_SUBCYCLE = 0, 1  # TE_COEF_COARSE_*: the coarsest level of the cycle with a coefficient
 
 
@@ -175,6 +176,9 @@ SYMBOLS = {
     "te_gradient": (_I, [_P, _I, _P, _P, _P]),
     "te_divergence": (_I, [_P, _I, _D, _P, _P]),
     "te_project": (_I, [_P, _I, _D, _P, _P, _P]),
+    "te_faces_from_cells": (_I, [_P, _I, _I, _P, _P, _P]),
+    "te_project_weighted": (_I, [_P, _I, _D, _P, _P, _P, _P]),
+    "te_add_boundary_rhs_weighted": (_I, [_P, _I, _P, _P, _P]),
     "te_faces_restrict": (_I, [_P, _I, _P, _P]),
     "te_gmg_set_coefficient": (_I, [_P, _P]),
     "te_gmg_has_coefficient": (_I, [_P]),
@@ -604,6 +608,20 @@ class GMG:
     def project(self, U, p, alpha=1.0, bdata=None, level=0):
         """U -= alpha grad p in one pass; collective"""
         check(lib().te_project(self.h, level, float(alpha), p.h, bdata.h if bdata is not None else None, U.h))
+
+    # ---- a variable-density step on the device (te_hip.h te_faces_from_cells): coefficient from a cell field, weighted projection, fold
+    def faces_from_cells(self, c, F, mode=FACE_MEAN, cb=None, level=0):
+        """F = the face values of the cell field c (FACE_MEAN, FACE_HARMONIC or FACE_RECIP_MEAN); cb: the field's values on the
+        physical faces, a boundary vector (None: the cell just inside). Single rank."""
+        check(lib().te_faces_from_cells(self.h, level, int(mode), c.h, cb.h if cb is not None else None, F.h))
+
+    def project_weighted(self, U, p, w, alpha=1.0, bdata=None, level=0):
+        """U -= alpha (w (.) grad p) in one pass, w a face vector distinct from U. Single rank."""
+        check(lib().te_project_weighted(self.h, level, float(alpha), p.h, bdata.h if bdata is not None else None, w.h, U.h))
+
+    def add_boundary_rhs_weighted(self, bdata, w, f, level=0):
+        """add_boundary_rhs with every datum multiplied first by the face weight w on its physical face, in place"""
+        check(lib().te_add_boundary_rhs_weighted(self.h, level, bdata.h, w.h, f.h))
 
     # ---- the variable-coefficient operator div(beta grad u) (te_hip.h: a second path, taken while a coefficient is set)
     def set_coefficient(self, beta):

@@ -16,6 +16,7 @@
 //   gmg_regrid.hip     the per-patch indicator te_patch_indicator and the transfer between two meshes te_vec_regrid (regridkernels.hpp)
 //   gmg_faceregrid.hip the transfer of a face vector between two meshes te_faces_regrid (faceregridkernels.hpp)
 //   gmg_coef.hip       the variable-coefficient operator div(beta grad u): coefficient per level, operator, sweeps, cycle (coefkernels.hpp)
+//   gmg_density.hip    the variable-density step around it: te_faces_from_cells, te_project_weighted, te_add_boundary_rhs_weighted (densitykernels.hpp)
 //   gmg_coefcoarse.hip its sub-patch coarse solve te_gmg_set_coef_coarse: the auxiliary solver on the split tree (coefcoarsekernels.hpp)
 #pragma once
 #include "capi_common.hpp"
@@ -112,7 +113,10 @@ enum KClass : int {
 	// restriction of the coefficient (cells = coarse sites)
 	KC_APPLY_COEF, KC_RESID_COEF, KC_JACOBI_COEF, KC_RBGS_COEF, KC_FACES_RESTRICT,
 	// the sub-patch coarse solve (coefcoarsekernels.hpp): one-patch level -> auxiliary level 0 (cells = doubles moved) and back
-	KC_COEF_SPLIT, KC_COEF_MERGE, KC_COUNT
+	KC_COEF_SPLIT, KC_COEF_MERGE,
+	// the variable-density step (densitykernels.hpp): face coefficients from a cell field (34.25 B per site at 32^3), the weighted
+	// projection (83.75), the fold of boundary data under a face weight (cells = boundary values)
+	KC_FACES_FROM_CELLS, KC_PROJECT_WEIGHTED, KC_BOUNDARY_RHS_W, KC_COUNT
 };
 extern const char *kclassName[KC_COUNT]; // (gmg_core.hip)
 

@@ -399,7 +399,8 @@ __global__ __launch_bounds__(256) void k_gradient2d(Level2D L, FaceGeom fg, cons
 		}
 	}
 }
-__global__ __launch_bounds__(256) void k_divergence2d(int P, int n, const double *__restrict__ hgeom, const double *__restrict__ U,
+// (inline: densitykernels.hpp includes this header in a second unit)
+inline __global__ __launch_bounds__(256) void k_divergence2d(int P, int n, const double *__restrict__ hgeom, const double *__restrict__ U,
                                                       double *__restrict__ out, double alpha)
 {
 	const int    h = n / 2;
