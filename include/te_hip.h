@@ -447,6 +447,8 @@ int te_gmg_set_allreduce(te_gmg *g, te_allreduce_fn fn, void *user);
  * pair by pair and in order. TE_ESTATE on ALL ranks when the ranks would issue different sequences (different
  * options or hierarchies) -- instead of a hang inside RCCL in the middle of a cycle. te_vcycle runs it by itself the
  * first time it sees a set of options on a sharded hierarchy (TE_NO_VERIFY skips that). Collective.
+ * With a coefficient set the dry run is the coefficient cycle's (the driver that will really run), and what has been verified is
+ * remembered per options, per "a coefficient is set" and per coarse-solver kind (te_gmg_set_coef_coarse).
  * Independently, a watchdog thread ends the process (exit status 86, message on stderr) when an exchange has not
  * completed TE_EXCHANGE_TIMEOUT seconds (default 300; 0 = off) after it was issued. */
 int te_gmg_verify_schedule(te_gmg *g, const te_cycle_opts *o);
@@ -590,7 +592,16 @@ int te_project(te_gmg *g, int level, double alpha, const te_vec *p, const te_vec
 
 /* The variable-coefficient operator A_b u = div(beta grad u): the pressure equation of a flow with variable density,
  * div((1 / rho) grad p) = div(u*) / dt. Nothing in the reference has it. A second, unfused path next to the Laplacian's, taken only
- * while a coefficient is set; with none set every call gives the bits it gave before these entry points existed. Single rank.
+ * while a coefficient is set; with none set every call gives the bits it gave before these entry points existed.
+ *
+ * SHARDED HIERARCHIES. te_faces_restrict, te_gmg_set_coefficient, te_gmg_set_reaction, te_gmg_set_coef_coarse,
+ * te_vcycle with a coefficient (TE_INTERP_DIRECT only), te_bicgstab with a coefficient and te_project_weighted are COLLECTIVE: every
+ * rank calls them, in the same order, each with the entries of its own patches. te_apply, te_residual, te_residual_norm_sq (this
+ * rank's part, as on the Laplacian path) and te_smooth with a coefficient are collective as they are without one. Results equal the
+ * single-rank run bit for bit: a child whose parent lives on another rank restricts its own block of beta and ships it, through the
+ * attached back-end (te_gmg_use_rccl or te_gmg_set_exchange; never the direct-store transport, which keeps serving the face
+ * ghosts). The collective set calls return TE_ESTATE (the message says "sharded") while NO transport is attached. Still single rank:
+ * TE_INTERP_LINEAR, te_fmg, te_patch_apply with a coefficient, the Schur route, te_faces_from_cells.
  *
  * beta is a FACE vector of the level (te_vec_create_faces: per patch LO_a then HI_a). A face shared by two patches is stored by
  * both: the caller keeps the two copies equal and every entry > 0; nothing checks this. rh2_a = 1 / h_a^2. u_lo / u_hi = the cell's
@@ -613,14 +624,17 @@ int te_project(te_gmg *g, int level, double alpha, const te_vec *p, const te_vec
  *              3D ((p00 + p10) + (p01 + p11)) * 0.25, 2D (p0 + p1) * 0.5 (te_boundary_restrict's associations). A patch that copies
  *              through hands its blocks on bit for bit. One writer per entry, no atomics.
  *
- * te_faces_restrict: coarse = that average of fine; face vectors of fine_level and fine_level + 1 (TE_EINVAL otherwise); TE_ESTATE
- * (the message says "sharded") on a sharded hierarchy.
+ * te_faces_restrict: coarse = that average of fine; face vectors of fine_level and fine_level + 1 (TE_EINVAL otherwise). Collective
+ * on a sharded hierarchy; TE_ESTATE (the message says "sharded") there while no transport is attached.
  * te_gmg_set_coefficient: beta = a level-0 face vector of this solver (TE_EINVAL otherwise). The solver COPIES it (the caller may free
  * or overwrite its vector) and restricts it level by level. The per-level copies are allocated at the first call and reused (a driver
  * calls this every time step); te_gmg_destroy frees them. NULL clears the coefficient and keeps the buffers;
- * te_gmg_release_workspace frees them too, but only while cleared. TE_ESTATE ("sharded") on a sharded hierarchy (NULL is accepted
- * there: nothing to clear). A call that fails after its checks leaves NO coefficient set, never a partly updated one.
- * te_gmg_has_coefficient: 0 or 1. te_gmg_coefficient: out = the level's beta (a face vector of that level); TE_ESTATE when none is set.
+ * te_gmg_release_workspace frees them too, but only while cleared. Collective on a sharded hierarchy (beta = this rank's patches;
+ * the send and receive buffers of the blocks that travel are made at the first such call and freed with the copies); TE_ESTATE
+ * ("sharded") there while no transport is attached (NULL is always accepted). A call that fails after its checks leaves NO
+ * coefficient set, never a partly updated one.
+ * te_gmg_has_coefficient: 0 or 1. te_gmg_coefficient: out = the level's beta (a face vector of that level: this rank's patches, on a
+ * level that lives on every rank all of it); TE_ESTATE when none is set.
  *
  * While a coefficient is set:
  *   te_apply, te_residual, te_residual_norm_sq use A_b (the norm is a second pass over r).
@@ -647,7 +661,8 @@ int te_gmg_coefficient(te_gmg *g, int level, te_vec *out);
 
 /* The reaction term: A_bs u = div(beta grad u) - sigma u, the operator of an implicit viscous or diffusive step
  * (rho / dt) u - div(mu grad u) = rhs, in this library's sign convention div(mu grad u) - (rho / dt) u = -rhs: beta = mu,
- * sigma = rho / dt, f = -rhs. sigma lives on the variable-coefficient path only. Single rank.
+ * sigma = rho / dt, f = -rhs. sigma lives on the variable-coefficient path only. Collective on a sharded
+ * hierarchy (te_restrict's blocks travel as they do for a residual).
  *
  * sigma is a CELL vector of the level (te_vec_create's layout), every entry >= 0; nothing checks this, exactly as with beta.
  *   operator   (A_bs u)[c] = (A_b u)[c] - sigma_c u_c: A_b evaluated exactly as written above, then one multiplication and one
@@ -660,12 +675,13 @@ int te_gmg_coefficient(te_gmg *g, int level, te_vec *out);
  * te_gmg_set_reaction: sigma = a level-0 cell vector of this solver (TE_EINVAL for a face, interface or boundary vector, another
  * level's or another solver's). The solver COPIES it and restricts it to every level, into per-level cell vectors allocated at the
  * first call and reused (a driver calls this every time step). NULL clears sigma and keeps the buffers. TE_ESTATE (the message says
- * "coefficient") unless a coefficient is set; TE_ESTATE ("sharded") on a sharded hierarchy. A call that fails after its checks
+ * "coefficient") unless a coefficient is set; TE_ESTATE ("sharded") on a sharded hierarchy without a transport. A call that fails after its checks
  * leaves NO sigma set. ORDER: every te_gmg_set_coefficient clears sigma, so per time step call te_gmg_set_coefficient first, then
  * te_gmg_set_reaction -- the operator is always what the last calls said, never a new beta with a stale sigma.
  * te_gmg_release_workspace frees the sigma buffers while sigma is cleared (and everything of the coefficient while that is
  * cleared); te_gmg_destroy always.
- * te_gmg_has_reaction: 0 or 1. te_gmg_reaction: out = the level's sigma (a cell vector of that level); TE_ESTATE when none is set.
+ * te_gmg_has_reaction: 0 or 1. te_gmg_reaction: out = the level's sigma (a cell vector of that level: this rank's patches); TE_ESTATE
+ * when none is set.
  *
  * While sigma is set te_apply, te_residual, te_residual_norm_sq, te_smooth (RB-GS, Jacobi), te_vcycle (V and W, both interpolators)
  * and te_bicgstab use A_bs; everything refused with a coefficient stays refused with the same codes. With sigma > 0 somewhere the
@@ -704,7 +720,7 @@ int te_gmg_reaction(te_gmg *g, int level, te_vec *out);
  * that is valid (the measured choice: DESIGN.md section 20), otherwise the smallest valid value, which is 4 where 4 is valid.
  * te_gmg_set_coef_coarse returns
  *   TE_EINVAL        unknown kind, cycles < 1, an invalid explicit sub_n;
- *   TE_ESTATE        a sharded hierarchy (the message says "sharded");
+ *   TE_ESTATE        a sharded hierarchy with no transport attached (the message says "sharded");
  *   TE_EUNSUPPORTED  the coarsest level has more than one patch (a truncated hierarchy; the message carries the count), or no valid
  *                    sub_n exists (n = 4 in 3D; in 2D an n whose halves never reach an even size >= 4, e.g. no multiple of 4);
  * and changes nothing then. With TE_COEF_COARSE_SWEEPS only kind and cycles are checked (sub_n is not used).
@@ -712,7 +728,10 @@ int te_gmg_reaction(te_gmg *g, int level, te_vec *out);
  * changes), on the parent's stream; te_gmg_release_workspace frees them while the kind is TE_COEF_COARSE_SWEEPS, te_gmg_destroy always.
  * te_gmg_profile and its companions act on the auxiliary solver too; its launches are counted in the parent's rows under their
  * existing names, the split and the merge as "coef_split" and "coef_merge".
- * te_gmg_coef_coarse: the current kind, the RESOLVED sub_n (0 while no sub-cycle has been selected) and cycles; NULL outputs are skipped. */
+ * te_gmg_coef_coarse: the current kind, the RESOLVED sub_n (0 while no sub-cycle has been selected) and cycles; NULL outputs are skipped.
+ * Sharded hierarchies: every rank calls te_gmg_set_coef_coarse and gets the same code (the patch count is the GLOBAL one). The auxiliary
+ * solver is single rank and exchanges nothing; a rank builds and runs it exactly when it holds the one coarsest patch -- every rank
+ * where that level lives on every rank, its owner otherwise -- and a rank without the patch does nothing at that point of the cycle. */
 #define TE_COEF_COARSE_SWEEPS   0 /* default: coarse_sweeps sweeps on the coarsest level */
 #define TE_COEF_COARSE_SUBCYCLE 1
 int te_gmg_set_coef_coarse(te_gmg *g, int kind, int sub_n, int cycles);
@@ -750,7 +769,8 @@ int te_gmg_coef_coarse(const te_gmg *g, int *kind, int *sub_n, int *cycles);
  * exactly te_gradient(p, bdata)'s value (the same ghosts; on a physical Neumann face g_n itself); t = w * G is one multiplication, then
  * U = fma(-alpha, t, U). With w = 1 everywhere the call gives te_project's bits; both copies of a same-level face get the same bits when
  * w's (and U's) copies agree. w = a face vector of the level, distinct from U. TE_EINVAL: w aliases U, wrong kinds, levels or solvers.
- * TE_ESTATE ("sharded") on a sharded hierarchy.
+ * Collective on a sharded hierarchy, as te_project is (bit for bit the single-rank result); TE_ESTATE ("sharded") there while no
+ * transport is attached.
  *
  * te_add_boundary_rhs_weighted(g, level, bdata, w, f): te_add_boundary_rhs with every datum multiplied first by w on its physical face,
  * b <- w_face * b (w_face = LO_a of the layer's cell on a lower side, HI_a on an upper side), then the same expressions: Dirichlet

@@ -616,7 +616,7 @@ class GMG:
         check(lib().te_faces_from_cells(self.h, level, int(mode), c.h, cb.h if cb is not None else None, F.h))
 
     def project_weighted(self, U, p, w, alpha=1.0, bdata=None, level=0):
-        """U -= alpha (w (.) grad p) in one pass, w a face vector distinct from U. Single rank."""
+        """U -= alpha (w (.) grad p) in one pass, w a face vector distinct from U; collective"""
         check(lib().te_project_weighted(self.h, level, float(alpha), p.h, bdata.h if bdata is not None else None, w.h, U.h))
 
     def add_boundary_rhs_weighted(self, bdata, w, f, level=0):
@@ -626,33 +626,36 @@ class GMG:
     # ---- the variable-coefficient operator div(beta grad u) (te_hip.h: a second path, taken while a coefficient is set)
     def set_coefficient(self, beta):
         """beta: a level-0 face vector (copied, then restricted to every level); None clears the coefficient.
-        Every call clears the reaction term: per step set beta first, then sigma (set_reaction)."""
+        Every call clears the reaction term: per step set beta first, then sigma (set_reaction).
+        Collective on a sharded hierarchy (each rank hands over its own patches' entries): blocks of beta travel to the ranks
+        that hold the parents."""
         check(lib().te_gmg_set_coefficient(self.h, beta.h if beta is not None else None))
 
     def has_coefficient(self):
         return bool(lib().te_gmg_has_coefficient(self.h))
 
     def coefficient(self, level, out):
-        """out (a face vector of `level`) = the solver's beta on that level"""
+        """out (a face vector of `level`) = the solver's beta on that level: this rank's patches (a replicated level: all of it)"""
         check(lib().te_gmg_coefficient(self.h, level, out.h))
 
     # ---- the reaction term: div(beta grad u) - sigma u (te_hip.h te_gmg_set_reaction; only while a coefficient is set)
     def set_reaction(self, sigma):
         """sigma: a level-0 cell vector, every entry >= 0 (copied, then restricted to every level); None clears it.
-        After set_coefficient, never before: set_coefficient clears sigma."""
+        After set_coefficient, never before: set_coefficient clears sigma. Collective on a sharded hierarchy."""
         check(lib().te_gmg_set_reaction(self.h, sigma.h if sigma is not None else None))
 
     def has_reaction(self):
         return bool(lib().te_gmg_has_reaction(self.h))
 
     def reaction(self, level, out):
-        """out (a cell vector of `level`) = the solver's sigma on that level"""
+        """out (a cell vector of `level`) = the solver's sigma on that level: this rank's patches"""
         check(lib().te_gmg_reaction(self.h, level, out.h))
 
     # ---- the coarsest level of the cycle with a coefficient (te_hip.h te_gmg_set_coef_coarse): a property of the solver
     def set_coef_coarse(self, kind, sub_n=0, cycles=2):
         """COEF_COARSE_SWEEPS (default: coarse_sweeps sweeps) or COEF_COARSE_SUBCYCLE: a one-patch coarsest level is split into
-        patches of sub_n cells per axis (0: in 3D 8 where valid, else the smallest valid size) and solved by `cycles` cycles of an auxiliary solver"""
+        patches of sub_n cells per axis (0: in 3D 8 where valid, else the smallest valid size) and solved by `cycles` cycles of an auxiliary solver.
+        Sharded: every rank calls it; the ranks that hold the coarsest patch run the (single-rank) auxiliary solver"""
         check(lib().te_gmg_set_coef_coarse(self.h, int(kind), int(sub_n), int(cycles)))
 
     def coef_coarse(self):
@@ -662,7 +665,7 @@ class GMG:
         return k.value, s.value, c.value
 
     def faces_restrict(self, fine_level, fine, coarse):
-        """coarse (a face vector of fine_level + 1) = the face average of fine"""
+        """coarse (a face vector of fine_level + 1) = the face average of fine; collective"""
         check(lib().te_faces_restrict(self.h, fine_level, fine.h, coarse.h))
 
     def add_boundary_rhs(self, bdata, f, level=0):

@@ -21,7 +21,9 @@
 //
 // The restriction of the coefficient, k_faces_restrict3d<N> / k_faces_restrict2d: level l + 1's beta = the face average of level
 // l's -- te_faces_regrid's "coarsen" rule (faceregridkernels.hpp coarsenPairX / coarsenPairT / face2d) through the level's child / copy
-// tables. One writer per entry; a patch that copies through hands its block on bit for bit.
+// tables. One writer per entry; a patch that copies through hands its block on bit for bit. Sharded hierarchies: a child whose parent
+// lives on another rank restricts itself into a block that travels (k_faces_restrict_pack3d / 2d), and the parent's rank picks its
+// entries from local children and received blocks alike (k_faces_restrict_recv3d / 2d): the same means, the same bits (see there).
 //
 // The reaction term: every operator / sweep kernel has a compile-time SIG and a pointer to the level's cell
 // vector sigma >= 0. SIG = true: apply (A_b u)[c] - sigma_c u_c (A_b as above, then one multiplication and one subtraction), residual
@@ -723,12 +725,137 @@ static __global__ __launch_bounds__(256) void k_faces_restrict2d(int n, int Pc, 
 			if (cp) return face2d(fine + (size_t) row[0] * FV, n, a, I, t);
 			const int     oa = I >= h, ob = t >= h;
 			const double *e = fine + (size_t) row[a == 0 ? oa + 2 * ob : ob + 2 * oa] * FV;
-			return (face2d(e, n, a, 2 * I - oa * n, 2 * t - ob * n) + face2d(e, n, a, 2 * I - oa * n, 2 * t - ob * n + 1)) * 0.5;
+			return faceMean2(face2d(e, n, a, 2 * I - oa * n, 2 * t - ob * n), face2d(e, n, a, 2 * I - oa * n, 2 * t - ob * n + 1));
 		};
 		*reinterpret_cast<double2 *>(dp + x + n * y)      = double2{value(0, x, y), value(0, x + 1, y)};
 		*reinterpret_cast<double2 *>(dp + nn + x + n * y) = double2{value(1, y, x), value(1, y, x + 1)};
 		if (x + 2 == n) dp[2 * nn + y] = value(0, n, y);
 		if (y == n - 1) *reinterpret_cast<double2 *>(dp + 2 * nn + n + x) = double2{value(1, n, x), value(1, n, x + 1)};
 	}
+}
+
+// ---- the coefficient on the next level when children live on other ranks. A child whose parent is not local
+// restricts ITSELF: its block is the face vector of a patch of m = n / 2 cells per axis (LO_a, a = 0 .. D-1, m^D each, then HI_a,
+// m^(D-1) each) -- every coarse face the child covers, its own lower plane 0 and its own HI_a included -- or, for a patch that
+// copies through, its n-cell face vector bit for bit. The parent's rank then only picks entries: nothing is averaged twice and
+// nothing is averaged on the other side of the wire, so every coarse entry is faceMean4 / faceMean2 of the same fine faces in the
+// same order as k_faces_restrict3d / 2d form it from a local child.
+
+// doubles of a face vector per patch of m cells per axis
+template <int D> __device__ __forceinline__ int faceVecSize(int m) { return D == 3 ? 3 * m * m * m + 3 * m * m : 2 * m * m + 2 * m; }
+
+// entry e of the face vector of m = n / 2 cells per axis that the fine patch fp (n cells per axis) restricts to
+template <int D> __device__ __forceinline__ double packedFaceEntry(const double *__restrict__ fp, int n, int e)
+{
+	const int m = n / 2, nn = n * n;
+	const int mc = D == 3 ? m * m * m : m * m, mf = D == 3 ? m * m : m;
+	const int nc = D == 3 ? nn * n : nn, nf = D == 3 ? nn : n;
+	if (e < D * mc) { // LO_a[c]: the fine LO_a faces of plane 2 c_a over the 2^(D-1) fine positions of the remaining axes
+		const int a = e / mc, c = e % mc;
+		if (D == 3) {
+			const double *q  = fp + (size_t) a * nc + 2 * (c % m) + n * 2 * ((c / m) % m) + nn * 2 * (c / (m * m));
+			const int     s0 = a == 0 ? n : 1, s1 = a == 2 ? n : nn; // strides of the lower / higher remaining axis
+			return faceMean4(q[0], q[s0], q[s1], q[s0 + s1]);
+		}
+		const double *q = fp + (size_t) a * nc + 2 * (c % m) + n * 2 * (c / m);
+		return faceMean2(q[0], q[a == 0 ? n : 1]);
+	}
+	const int     h = e - D * mc, a = h / mf, t = h % mf; // HI_a[t]: the same over the fine patch's HI_a block
+	const double *q = fp + (size_t) D * nc + (size_t) a * nf;
+	if (D == 3) {
+		q += 2 * (t % m) + n * 2 * (t / m);
+		return faceMean4(q[0], q[1], q[n], q[n + 1]);
+	}
+	return faceMean2(q[2 * t], q[2 * t + 1]);
+}
+
+// one workgroup per up block (fine patch, orthant or -1) of the level's transfer tables: out + foff[block] <- the block
+template <int D>
+__device__ __forceinline__ void facesPackBlock(int n, const int32_t *__restrict__ desc, const int64_t *__restrict__ foff, const double *__restrict__ fine,
+                                               double *__restrict__ out)
+{
+	const int     b = blockIdx.x, tid = threadIdx.x, TPB = blockDim.x;
+	const int     p = desc[2 * b], o = desc[2 * b + 1];
+	const int     FVn = faceVecSize<D>(n), FVm = faceVecSize<D>(n / 2);
+	const double *fp  = fine + (size_t) p * FVn;
+	double       *dst = out + foff[b];
+	if (o < 0) { // a patch that copies through: bit for bit
+		for (int i = tid; i < FVn; i += TPB) dst[i] = fp[i];
+		return;
+	}
+	for (int e = tid; e < FVm; e += TPB) dst[e] = packedFaceEntry<D>(fp, n, e);
+}
+template <int N>
+__global__ __launch_bounds__(256) void k_faces_restrict_pack3d(const int32_t *__restrict__ desc, const int64_t *__restrict__ foff,
+                                                               const double *__restrict__ fine, double *__restrict__ out)
+{
+	facesPackBlock<3>(N, desc, foff, fine, out);
+}
+static __global__ __launch_bounds__(256) void k_faces_restrict_pack2d(int n, const int32_t *__restrict__ desc, const int64_t *__restrict__ foff,
+                                                                      const double *__restrict__ fine, double *__restrict__ out)
+{
+	facesPackBlock<2>(n, desc, foff, fine, out);
+}
+
+// The coarse side on a rank that received blocks: entry e of coarse patch pc (row = its children, >= 0 a local fine patch, <= -2
+// block -(row[o] + 2) of recv at foff). The child that covers a coarse face (a, I, t): o_a = (I >= m), the other bits from t; in its
+// restricted face vector the face is local plane I - o_a m of LO_a -- for I = m that is plane 0 of the UPPER child -- and for
+// I = n the upper child's HI_a. A local child: packedFaceEntry of its fine patch, the bits of k_faces_restrict3d / 2d.
+template <int D>
+__device__ __forceinline__ double coarseFaceEntry(int n, const int32_t *__restrict__ row, bool cp, const double *__restrict__ fine,
+                                                  const double *__restrict__ recv, const int64_t *__restrict__ foff, int e)
+{
+	const int m = n / 2, nn = n * n, FVn = faceVecSize<D>(n);
+	const int mc = D == 3 ? m * m * m : m * m, mf = D == 3 ? m * m : m;
+	const int nc = D == 3 ? nn * n : nn, nf = D == 3 ? nn : n;
+	if (cp) {
+		const int ch = row[0];
+		return ch >= 0 ? fine[(size_t) ch * FVn + e] : recv[foff[-(ch + 2)] + e];
+	}
+	int o, em;
+	if (e < D * nc) {
+		const int a = e / nc, c = e % nc;
+		const int cx = c % n, cy = D == 3 ? (c / n) % n : c / n, cz = D == 3 ? c / nn : 0;
+		const int ox = cx >= m, oy = cy >= m, oz = cz >= m;
+		o  = ox + 2 * oy + 4 * oz;
+		em = a * mc + (cx - ox * m) + m * (cy - oy * m) + m * m * (cz - oz * m);
+	} else {
+		const int h = e - D * nc, a = h / nf, t = h % nf;
+		const int t0 = D == 3 ? t % n : t, t1 = D == 3 ? t / n : 0; // the remaining axes, the lower one first
+		const int o0 = t0 >= m, o1 = t1 >= m;
+		if (D == 3)
+			o = a == 0 ? 1 + 2 * o0 + 4 * o1 : (a == 1 ? o0 + 2 + 4 * o1 : o0 + 2 * o1 + 4);
+		else
+			o = a == 0 ? 1 + 2 * o0 : o0 + 2;
+		em = D * mc + a * mf + (t0 - o0 * m) + m * (t1 - o1 * m);
+	}
+	const int ch = row[o];
+	return ch >= 0 ? packedFaceEntry<D>(fine + (size_t) ch * FVn, n, em) : recv[foff[-(ch + 2)] + em];
+}
+
+// one thread per coarse entry, in address order: one writer per entry, stores along x
+template <int D>
+__device__ __forceinline__ void facesRestrictRecv(int n, int Pc, const int32_t *__restrict__ child, const int32_t *__restrict__ copy,
+                                                  const double *__restrict__ fine, const double *__restrict__ recv, const int64_t *__restrict__ foff,
+                                                  double *__restrict__ coarse)
+{
+	const size_t FVn = (size_t) faceVecSize<D>(n), total = (size_t) Pc * FVn;
+	for (size_t idx = (size_t) blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (size_t) gridDim.x * blockDim.x) {
+		const int pc = (int) (idx / FVn), e = (int) (idx % FVn);
+		coarse[idx]  = coarseFaceEntry<D>(n, child + (size_t) pc * (1 << D), copy[pc] != 0, fine, recv, foff, e);
+	}
+}
+template <int N>
+__global__ __launch_bounds__(256) void k_faces_restrict_recv3d(int Pc, const int32_t *__restrict__ child, const int32_t *__restrict__ copy,
+                                                               const double *__restrict__ fine, const double *__restrict__ recv,
+                                                               const int64_t *__restrict__ foff, double *__restrict__ coarse)
+{
+	facesRestrictRecv<3>(N, Pc, child, copy, fine, recv, foff, coarse);
+}
+static __global__ __launch_bounds__(256) void k_faces_restrict_recv2d(int n, int Pc, const int32_t *__restrict__ child, const int32_t *__restrict__ copy,
+                                                                      const double *__restrict__ fine, const double *__restrict__ recv,
+                                                                      const int64_t *__restrict__ foff, double *__restrict__ coarse)
+{
+	facesRestrictRecv<2>(n, Pc, child, copy, fine, recv, foff, coarse);
 }
 } // namespace te

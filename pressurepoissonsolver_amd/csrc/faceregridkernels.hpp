@@ -69,19 +69,25 @@ template <int N> __device__ __forceinline__ int faceOff(int comp, int cx, int cy
 	return cz < N ? 2 * NNN + cx + N * cy + NN * cz : 3 * NNN + 2 * NN + cx + N * cy;
 }
 
+// THE mean of the fine faces that cover a coarse face, for every kernel that coarsens a face vector (the transfer between two meshes
+// here, the restriction of the coefficient and its packed form for parents on other ranks in coefkernels.hpp): p[i][j] = the fine
+// face at offset i along the lower and j along the higher remaining axis. One place, so the association cannot drift.
+__device__ __forceinline__ double faceMean4(double p00, double p10, double p01, double p11) { return ((p00 + p10) + (p01 + p11)) * 0.25; }
+__device__ __forceinline__ double faceMean2(double p0, double p1) { return (p0 + p1) * 0.5; }
+
 // a pair of coarse faces whose lower remaining axis runs fastest in memory: q = the first fine face of the first one, s2 = the
 // stride of the other remaining axis
 __device__ __forceinline__ double2 coarsenPairT(const double *q, int s2)
 {
 	const double2 a = *reinterpret_cast<const double2 *>(q), b = *reinterpret_cast<const double2 *>(q + 2);
 	const double2 c = *reinterpret_cast<const double2 *>(q + s2), d = *reinterpret_cast<const double2 *>(q + s2 + 2);
-	return double2{((a.x + a.y) + (c.x + c.y)) * 0.25, ((b.x + b.y) + (d.x + d.y)) * 0.25};
+	return double2{faceMean4(a.x, a.y, c.x, c.y), faceMean4(b.x, b.y, d.x, d.y)};
 }
 // LO_x: the pair lies along the normal (fine planes q, q + 2), the remaining axes are y (stride N) and z (stride NN)
 template <int N> __device__ __forceinline__ double2 coarsenPairX(const double *q)
 {
 	constexpr int NN = N * N;
-	return double2{((q[0] + q[N]) + (q[NN] + q[N + NN])) * 0.25, ((q[2] + q[N + 2]) + (q[NN + 2] + q[N + NN + 2])) * 0.25};
+	return double2{faceMean4(q[0], q[N], q[NN], q[N + NN]), faceMean4(q[2], q[N + 2], q[NN + 2], q[N + NN + 2])};
 }
 
 // the three values a one-sided central difference along an axis needs at index c of 0 .. N-1: (c - 1, c + 1) inside, the three
@@ -318,7 +324,7 @@ __device__ __forceinline__ double coarsenFace2d(const double *src, size_t FV, co
 {
 	const int     h = n / 2, oa = I >= h, ob = t >= h;
 	const double *e = src + (size_t) row[2 + (a == 0 ? oa + 2 * ob : ob + 2 * oa)] * FV;
-	return (face2d(e, n, a, 2 * I - oa * n, 2 * t - ob * n) + face2d(e, n, a, 2 * I - oa * n, 2 * t - ob * n + 1)) * 0.5;
+	return faceMean2(face2d(e, n, a, 2 * I - oa * n, 2 * t - ob * n), face2d(e, n, a, 2 * I - oa * n, 2 * t - ob * n + 1));
 }
 
 static __global__ __launch_bounds__(256) void k_facexfer2d(int n, int Pd, const int32_t *__restrict__ map, const double *__restrict__ hsrc,

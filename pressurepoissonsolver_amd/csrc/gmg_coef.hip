@@ -49,18 +49,69 @@ static int checkFaces(te_gmg *g, int level, const te_vec *v, const char *who)
 		return te::fail(TE_EINVAL, std::string(who) + ": not a face vector of level " + std::to_string(level) + " of this solver");
 	return TE_OK;
 }
-static int refuseSharded(const te_gmg *g, const char *who)
+
+// g->coef, and on a sharded hierarchy the device side of every level's face restriction across ranks (CoefWs::fxfer): block offsets,
+// send and receive buffer, sized from the level's face totals. A level on which this rank sends and receives nothing allocates nothing.
+static int coefWorkspace(te_gmg *g)
 {
-	if (g->nranks > 1) return te::fail(TE_ESTATE, std::string(who) + ": not implemented on a sharded hierarchy (single rank only)");
+	if (!g->coef) g->coef = new CoefWs;
+	CoefWs &W = *g->coef;
+	if (g->nranks == 1 || !W.fxfer.empty()) return TE_OK;
+	HIPCHK(hipSetDevice(g->device));
+	std::vector<std::unique_ptr<CoefFaceXfer>> fx;
+	for (auto &L : g->levels) {
+		auto X = std::make_unique<CoefFaceXfer>();
+		int  rc;
+		if ((rc = X->up_foff.upload(L->up_foff_host)) || (rc = X->down_foff.upload(L->down_foff_host))
+		    || (rc = X->up.alloc((size_t) L->up_ftotal)) || (rc = X->down.alloc((size_t) L->down_ftotal)))
+			return rc;
+		fx.push_back(std::move(X));
+	}
+	W.fxfer = std::move(fx);
 	return TE_OK;
 }
 
-// coarse = the face average of fine (level l -> l + 1), through level l's child / copy tables
+// coarse = the face average of fine (level l -> l + 1), through level l's child / copy tables. Sharded: children whose parent lives
+// on another rank (under repl_up: every local patch, one copy for everybody) restrict themselves into their block of the send
+// buffer, the blocks travel through the attached back-end under a tag of their own, and the coarse side picks its entries from
+// local children and received blocks alike (coefkernels.hpp). Recording: nothing moves, the exchange is recorded.
 static int facesRestrict(te_gmg *g, int l, const double *fine, double *coarse)
 {
-	LevelHost &L = *g->levels[l];
+	LevelHost    &L = *g->levels[l];
+	CoefFaceXfer *X = nullptr;
+	int           rc;
+	if (g->nranks > 1) {
+		if ((rc = coefWorkspace(g))) return rc;
+		X = g->coef->fxfer[l].get();
+		if (L.n_up > 0 && L.up_ftotal > 0) {
+			Timed t(g, KC_PACK, (size_t) L.up_ftotal);
+			if (L.dim == 2)
+				hipLaunchKernelGGL(k_faces_restrict_pack2d, dim3(L.n_up), dim3(256), 0, g->stream, L.n, L.up_desc.p, X->up_foff.p, fine, X->up.p);
+			else
+				dispatchN(L.n, [&](auto n) {
+					hipLaunchKernelGGL(k_faces_restrict_pack3d<decltype(n)::value>, dim3(L.n_up), dim3(256), 0, g->stream, L.up_desc.p, X->up_foff.p, fine,
+					                   X->up.p);
+				});
+			HIPCHK(hipGetLastError());
+		}
+		if ((rc = doExchange(g, 4, L.tx_fup, X->up.p, X->down.p))) return rc; // (tags 1 - 3: faces, restriction, prolongation)
+	}
 	if (L.Pc == 0) return TE_OK;
 	Timed t(g, KC_FACES_RESTRICT, (size_t) L.Pc * L.nc);
+	if (X && L.n_down > 0) { // some child's block was received: the form that reads local children and blocks alike
+		const size_t FV   = (size_t) L.dim * L.nc + (size_t) L.dim * L.nf;
+		const dim3   grid(gridFor((size_t) L.Pc * FV, 256, 65536));
+		if (L.dim == 2)
+			hipLaunchKernelGGL(k_faces_restrict_recv2d, grid, dim3(256), 0, g->stream, L.n, L.Pc, L.child.p, L.copy.p, fine, (const double *) X->down.p,
+			                   X->down_foff.p, coarse);
+		else
+			dispatchN(L.n, [&](auto n) {
+				hipLaunchKernelGGL(k_faces_restrict_recv3d<decltype(n)::value>, grid, dim3(256), 0, g->stream, L.Pc, L.child.p, L.copy.p, fine,
+				                   (const double *) X->down.p, X->down_foff.p, coarse);
+			});
+		HIPCHK(hipGetLastError());
+		return TE_OK;
+	}
 	if (L.dim == 2)
 		hipLaunchKernelGGL(k_faces_restrict2d, dim3(gridFor((size_t) L.Pc * L.nc / 2, 256, 65536)), dim3(256), 0, g->stream, L.n, L.Pc, L.child.p,
 		                   L.copy.p, fine, coarse);
@@ -259,9 +310,12 @@ int vcycleCoef(te_gmg *g, const te_cycle_opts *o, const te_vec *f, te_vec *u)
 	int rc;
 	if (!o) return te::fail(TE_EINVAL, "te_vcycle: null options");
 	if ((rc = checkLevelVec(g, 0, f, "te_vcycle")) || (rc = checkLevelVec(g, 0, u, "te_vcycle"))) return rc;
-	if ((rc = refuseSharded(g, "te_vcycle with a coefficient"))) return rc;
 	if (o->smoother != TE_SMOOTH_RBGS && o->smoother != TE_SMOOTH_JACOBI)
 		return te::fail(TE_EUNSUPPORTED, "te_vcycle: with a coefficient set only TE_SMOOTH_RBGS and TE_SMOOTH_JACOBI exist");
+	// several ranks: the placement check and, with new options, the dry run of the driver below (gmg_cycle.hip), as te_vcycle does
+	// without a coefficient
+	if ((rc = verifyBeforeCycle(g, o))) return rc;
+	// (what CycleScope does around visit(): this driver keeps no compact x faces and no face-layer iterates, so nothing but the reset)
 	for (auto &L : g->levels) L->xf_valid_for = nullptr, L->ps_faces = false;
 	if ((rc = te_vec_set(u, 0.0))) return rc; // Cycle.h:118
 	rc           = visitCoef(g, o, 0, f, u);
@@ -276,7 +330,7 @@ int te_faces_restrict(te_gmg *g, int fine_level, const te_vec *fine, te_vec *coa
 	return guarded([&]() -> int {
 		int rc;
 		if (!g) return te::fail(TE_EINVAL, "te_faces_restrict: null solver");
-		if ((rc = refuseSharded(g, "te_faces_restrict"))) return rc;
+		if ((rc = shardedNeedsTransport(g, "te_faces_restrict"))) return rc;
 		if (fine_level < 0 || fine_level + 1 >= (int) g->levels.size()) return te::fail(TE_EINVAL, "te_faces_restrict: no coarser level below this one");
 		if ((rc = checkFaces(g, fine_level, fine, "te_faces_restrict")) || (rc = checkFaces(g, fine_level + 1, coarse, "te_faces_restrict"))) return rc;
 		return facesRestrict(g, fine_level, fine->d, coarse->d);
@@ -290,15 +344,15 @@ int te_gmg_set_coefficient(te_gmg *g, const te_vec *beta)
 		if (!g) return te::fail(TE_EINVAL, "te_gmg_set_coefficient: null solver");
 		for (auto &L : g->levels) L->xf_valid_for = nullptr; // (the operator changes)
 		if (g->coef) g->coef->sigma_on = false; // every call clears sigma: never a new beta with a stale sigma (the order per step is beta, then sigma)
-		if (!beta) { // (also on a sharded hierarchy, where none can be set: nothing to clear)
+		if (!beta) { // (nothing to clear where none is set)
 			g->coef_on = false;
 			return coefCoarseRefresh(g, true);
 		}
-		if ((rc = refuseSharded(g, "te_gmg_set_coefficient"))) return rc;
+		if ((rc = shardedNeedsTransport(g, "te_gmg_set_coefficient"))) return rc;
 		if ((rc = checkFaces(g, 0, beta, "te_gmg_set_coefficient"))) return rc;
 		const int nl = (int) g->levels.size();
-		if (!g->coef) {
-			g->coef = new CoefWs;
+		if ((rc = coefWorkspace(g))) return rc;
+		if (g->coef->beta.empty()) {
 			g->coef->beta.assign(nl, nullptr);
 			for (int l = 0; l < nl; l++)
 				if ((rc = te_vec_create_faces(g, l, &g->coef->beta[l]))) {
@@ -345,7 +399,7 @@ int te_gmg_set_reaction(te_gmg *g, const te_vec *sigma)
 			if (g->coef) g->coef->sigma_on = false;
 			return coefCoarseRefresh(g, false);
 		}
-		if ((rc = refuseSharded(g, "te_gmg_set_reaction"))) return rc;
+		if ((rc = shardedNeedsTransport(g, "te_gmg_set_reaction"))) return rc;
 		if (!g->coef_on || !g->coef)
 			return te::fail(TE_ESTATE, "te_gmg_set_reaction: no coefficient is set (sigma lives on the coefficient path: te_gmg_set_coefficient first, "
 			                           "a face vector of ones for the Laplacian)");

@@ -2,7 +2,9 @@
 // patch of n^D cells is the same grid as a uniform tree of (n / s)^D patches of s^D cells, and on that tree the path's own kernels and
 // its own coarse levels exist. The parent solver owns an AUXILIARY solver on that tree -- an ordinary te_gmg that borrows the parent's
 // stream (gmgCreate) -- and visitCoef hands its coarsest level to coefCoarseSolve: split f and u, `cycles` cycles of visitCoef on the
-// auxiliary solver with the caller's options, merge u. No event and no host synchronisation inside a cycle. Single rank.
+// auxiliary solver with the caller's options, merge u. No event and no host synchronisation inside a cycle. On a sharded hierarchy the
+// auxiliary solver stays single rank and exchanges nothing: the ranks that hold the one coarsest patch (every rank where the level is
+// replicated, its owner otherwise) build and run it, the others do nothing at that point of the cycle.
 #include "gmg_internal.hpp"
 #include "coefcoarsekernels.hpp"
 
@@ -104,6 +106,8 @@ int coefCoarseRefresh(te_gmg *g, bool with_beta)
 
 int coefCoarseSolve(te_gmg *g, const te_cycle_opts *o, const te_vec *f, te_vec *u)
 {
+	// a rank without the coarsest patch has no part in it; the schedule check's dry run skips it (it exchanges nothing)
+	if (g->levels.back()->P == 0 || g->recording) return TE_OK;
 	CoefCoarseWs *W = g->cc;
 	if (!W || !W->aux || !W->aux->coef_on || !W->aux->coef)
 		return te::fail(TE_ESTATE, "te_vcycle: the sub-patch coarse solve has no coefficient (te_gmg_set_coef_coarse)");
@@ -189,8 +193,8 @@ int te_gmg_set_coef_coarse(te_gmg *g, int kind, int sub_n, int cycles)
 		const int D = g->dim, n = g->n;
 		if (sub_n != 0 && !subShapeOk(D, sub_n))
 			return te::fail(TE_EINVAL, std::string("te_gmg_set_coef_coarse: sub_n must be even and at least 4") + (D == 3 ? ", in 3D one of 4, 8, 16" : ""));
-		if (g->nranks > 1) return te::fail(TE_ESTATE, "te_gmg_set_coef_coarse: not implemented on a sharded hierarchy (single rank only)");
-		if (g->coarse_P_global != 1)
+		if ((rc = shardedNeedsTransport(g, "te_gmg_set_coef_coarse"))) return rc;
+		if (g->coarse_P_global != 1) // (the global count: every rank of a sharded hierarchy returns the same code)
 			return te::fail(TE_EUNSUPPORTED, "te_gmg_set_coef_coarse: the coarsest level has " + std::to_string(g->coarse_P_global)
 			                                     + " patches; the sub-patch coarse solve needs a coarsest level of one patch");
 		if (sub_n != 0 && !subValid(D, n, sub_n))
@@ -208,7 +212,8 @@ int te_gmg_set_coef_coarse(te_gmg *g, int kind, int sub_n, int cycles)
 			HIPCHK(hipStreamSynchronize(g->stream));
 			coefCoarseFree(g);
 		}
-		if (!g->cc && (rc = coefCoarseBuild(g, s))) return rc;
+		// (sharded: only a rank that holds the one coarsest patch has an auxiliary solver; the others keep the settings alone)
+		if (!g->cc && g->levels.back()->P == 1 && (rc = coefCoarseBuild(g, s))) return rc;
 		g->cc_sub_n        = s; // (what the auxiliary solver has, whatever follows)
 		const int old_kind = g->cc_kind;
 		g->cc_kind         = kind;

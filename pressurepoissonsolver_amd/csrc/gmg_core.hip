@@ -84,6 +84,8 @@ int buildLevel(te_gmg *g, const Hierarchy &H, int li)
 	L->tx_up = std::move(T.tx_up), L->tx_down = std::move(T.tx_down), L->tx_direct = std::move(T.tx_direct);
 	L->prolong_fusable = T.prolong_fusable, L->prolong_fusable_cf = T.prolong_fusable_cf, L->has_copy = T.has_copy;
 	L->repl_up = T.repl_up, L->repl_direct = T.repl_direct, L->post_exchange_free = T.post_exchange_free;
+	L->tx_fup = std::move(T.tx_fup), L->up_foff_host = std::move(T.up_foff), L->down_foff_host = std::move(T.down_foff);
+	L->up_ftotal = T.up_ftotal, L->down_ftotal = T.down_ftotal;
 
 	// (an empty table allocates nothing)
 	const size_t P1 = (size_t) std::max(T.P, 1), nf = T.nf;

@@ -299,9 +299,9 @@ static int verifySchedule(te_gmg *g, const te_cycle_opts *o)
 	g->profiling    = false;
 	g->recording    = true;
 	g->record.clear();
-	{
+	{ // the driver that will really run: with a coefficient set the plain one of gmg_coef.hip
 		CycleScope in(g);
-		rc = visit(g, o, 0, f, u, o->fuse != 0);
+		rc = g->coef_on ? visitCoef(g, o, 0, f, u) : visit(g, o, 0, f, u, o->fuse != 0);
 	}
 	g->recording = false;
 	g->profiling = prof;
@@ -392,12 +392,29 @@ static int checkPlacement(te_gmg *g)
 	return TE_OK;
 }
 
-static uint64_t optsKey(const te_cycle_opts *o)
+// what a verified schedule was verified for: the options, and with a coefficient set that fact and the coarse-solver kind (another
+// driver, and a coarsest level that sweeps -- with exchanges -- or hands over to the auxiliary solver, which has none)
+static uint64_t optsKey(const te_gmg *g, const te_cycle_opts *o)
 {
 	uint64_t h = 0;
 	for (int32_t v : {o->pre_sweeps, o->post_sweeps, o->coarse_sweeps, o->mid_sweeps, o->cycle_type, o->smoother, o->exact_coarse, o->fuse})
 		h = mix64(h, (uint64_t) (uint32_t) v);
+	if (g->coef_on) h = mix64(mix64(h, 0xC0EFull), (uint64_t) (uint32_t) g->cc_kind);
 	return h;
+}
+
+// several ranks: the first cycle with a new set of options checks that all ranks will issue matching exchange
+// sequences (a mismatch would otherwise be a silent hang inside RCCL); TE_NO_VERIFY skips it
+int verifyBeforeCycle(te_gmg *g, const te_cycle_opts *o)
+{
+	int rc;
+	if (!g->recording && (rc = checkPlacement(g))) return rc;
+	if (g->nranks > 1 && !g->recording && (g->rccl.comm || g->allreduce) && !g->verified_opts.count(optsKey(g, o))
+	    && !g->cfg.has(O_NO_VERIFY)) {
+		if ((rc = verifySchedule(g, o))) return rc;
+		g->verified_opts.insert(optsKey(g, o));
+	}
+	return TE_OK;
 }
 
 // te_vcycle; `pending`: f is still to be formed (te_bicgstab; consumed by level 0's first reader, visit())
@@ -411,14 +428,7 @@ int vcycleWith(te_gmg *g, const te_cycle_opts *o, const te_vec *f, te_vec *u, co
 	int rc;
 	if (!o) return te::fail(TE_EINVAL, "te_vcycle: null options");
 	if ((rc = checkLevelVec(g, 0, f, "te_vcycle")) || (rc = checkLevelVec(g, 0, u, "te_vcycle"))) return rc;
-	// several ranks: the first cycle with a new set of options checks that all ranks will issue matching exchange
-	// sequences (a mismatch would otherwise be a silent hang inside RCCL); TE_NO_VERIFY skips it
-	if (!g->recording && (rc = checkPlacement(g))) return rc;
-	if (g->nranks > 1 && !g->recording && (g->rccl.comm || g->allreduce) && !g->verified_opts.count(optsKey(o))
-	    && !g->cfg.has(O_NO_VERIFY)) {
-		if ((rc = verifySchedule(g, o))) return rc;
-		g->verified_opts.insert(optsKey(o));
-	}
+	if ((rc = verifyBeforeCycle(g, o))) return rc;
 	if (!o->fuse && (rc = te_vec_set(u, 0.0))) return rc; // Cycle.h:118
 	const double *keep;
 	{
@@ -570,7 +580,7 @@ int te_gmg_verify_schedule(te_gmg *g, const te_cycle_opts *o)
 	return guarded([&]() -> int {
 		if (!g || !o) return te::fail(TE_EINVAL, "te_gmg_verify_schedule: null argument");
 		int rc = verifySchedule(g, o);
-		if (rc == TE_OK) g->verified_opts.insert(optsKey(o));
+		if (rc == TE_OK) g->verified_opts.insert(optsKey(g, o));
 		return rc;
 	});
 }

@@ -2,7 +2,8 @@
 // field (te_faces_from_cells), the weighted projection in one pass (te_project_weighted) and the fold of boundary data under a face
 // weight (te_add_boundary_rhs_weighted). All three are additive: none reads or changes the coefficient of te_gmg_set_coefficient.
 // te_faces_from_cells fills the level's coarse/fine ghost slots itself (raw cells, no exchange: single rank); te_project_weighted
-// makes the level's ghosts current exactly as te_project does (withGhosts / prepareGhosts2d). Either way the next te_apply refills
+// makes the level's ghosts current exactly as te_project does (withGhosts / prepareGhosts2d: collective on a sharded hierarchy, the
+// launch runs per interior / boundary subset and reads w and U of its own patches only). Either way the next te_apply refills
 // the slots from its own iterate, as every operator call does.
 #include "gmg_ghosts3d.hpp"
 #include "densitykernels.hpp"
@@ -106,7 +107,7 @@ int te_project_weighted(te_gmg *g, int level, double alpha, const te_vec *p, con
 		    || (rc = checkKind(g, level, w, true, false, who, "w: a face vector")) || (rc = checkKind(g, level, U, true, false, who, "U: a face vector")))
 			return rc;
 		if (w == U || w->d == U->d) return te::fail(TE_EINVAL, std::string(who) + ": w and U must be different vectors");
-		if ((rc = refuseShardedDensity(g, who))) return rc;
+		if ((rc = shardedNeedsTransport(g, who))) return rc;
 		LevelHost &L = *g->levels[level];
 		if (L.P == 0) return TE_OK;
 		FaceGeom G;

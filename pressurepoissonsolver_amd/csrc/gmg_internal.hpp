@@ -72,12 +72,6 @@ struct te_vec {
 	bool    faces = false; // a face vector of the level (te_vec_create_faces): per local patch dim n^dim + dim n^(dim-1) doubles
 };
 
-struct CoefWs { // te_gmg::coef (gmg_coef.hip)
-	std::vector<te_vec *> beta;  // [level] face vectors of the solver
-	std::vector<te_vec *> sigma; // [level] cell vectors of the solver: the reaction term (te_gmg_set_reaction); empty until the first call
-	bool                  sigma_on = false; // the operator is A_b,sigma = A_b - sigma (DESIGN.md section 19)
-};
-
 namespace tei
 {
 enum KClass : int {
@@ -189,6 +183,23 @@ template <typename T> struct DevBuf {
 	}
 };
 
+// one level's face-restriction buffers on a sharded hierarchy (CoefWs::fxfer): offsets of the up / down blocks, send and receive buffer
+struct CoefFaceXfer {
+	DevBuf<int64_t> up_foff, down_foff;
+	DevBuf<double>  up, down;
+};
+
+} // namespace tei
+struct CoefWs { // te_gmg::coef (gmg_coef.hip)
+	std::vector<te_vec *> beta;  // [level] face vectors of the solver; empty until the first te_gmg_set_coefficient
+	// sharded hierarchies: per level the device side of the face restriction to parents on other ranks (LevelHost::tx_fup), made by
+	// the first sharded te_gmg_set_coefficient / te_faces_restrict and freed with this workspace; empty on one rank
+	std::vector<std::unique_ptr<tei::CoefFaceXfer>> fxfer; // [level]
+	std::vector<te_vec *> sigma; // [level] cell vectors of the solver: the reaction term (te_gmg_set_reaction); empty until the first call
+	bool                  sigma_on = false; // the operator is A_b,sigma = A_b - sigma (DESIGN.md section 19)
+};
+namespace tei
+{
 struct LevelHost;
 // 2D, opts.fuse >= 2: the ghost terms of a coarse right-hand side that the FINER level's pre-sweep left out and that no fix-up pass
 // has added: the coarse level's own pre-sweep adds them (k_rbgs_zero_resid2d_lds<.., FOLD>). fine == null: nothing pending.
@@ -243,6 +254,11 @@ struct LevelHost {
 	DevBuf<int32_t> up_desc, down_desc; // [n][2] (patch, orthant)
 	DevBuf<int64_t> up_off, down_off;   // block offsets inside upbuf / downbuf
 	DevBuf<double>  upbuf, downbuf;
+	// the same blocks with face-vector sizes (level_tables.hpp up_foff / tx_fup): the restriction of a face vector to parents on
+	// other ranks. Host tables only; the device copies and the two buffers belong to the coefficient workspace (CoefFaceXfer)
+	ExPlan               tx_fup;
+	std::vector<int64_t> up_foff_host, down_foff_host;
+	int64_t              up_ftotal = 0, down_ftotal = 0;
 	// patch solve
 	DevBuf<int32_t> plan, zero_mode;
 	DevBuf<int32_t> bcgs_its; // [P]: iterations of the last TE_SMOOTH_PATCH_BCGS sweep on this level (allocated on first use)
@@ -799,6 +815,15 @@ inline int coefRefuse(const te_gmg *g, const char *who)
 		return te::fail(TE_ESTATE, std::string(who) + ": not available while a coefficient is set (te_gmg_set_coefficient(g, NULL) clears it)");
 	return TE_OK;
 }
+// The collective calls of the coefficient path on a sharded hierarchy (te_gmg_set_coefficient, te_gmg_set_reaction, te_faces_restrict,
+// te_gmg_set_coef_coarse, te_project_weighted) are refused up front while no transport is attached: they would otherwise fail at
+// their first exchange, half way through and on some ranks only.
+inline int shardedNeedsTransport(const te_gmg *g, const char *who)
+{
+	if (g->nranks > 1 && !g->rccl.comm && !g->exchange)
+		return te::fail(TE_ESTATE, std::string(who) + ": collective on a sharded hierarchy: attach a transport first (te_gmg_set_exchange or te_gmg_use_rccl)");
+	return TE_OK;
+}
 // ---- gmg_launch2d.hip
 int prepareGhosts2d(te_gmg *g, LevelHost &L, const double *u, bool patch_op = false);
 template <int MODE> int launchStencil2d(te_gmg *g, LevelHost &L, const double *u, const double *f, double *out, double omega, int redmode = RED_NONE,
@@ -826,6 +851,7 @@ void schurFree(te_gmg *g); // (te_gmg_destroy)
 int visit(te_gmg *g, const te_cycle_opts *o, int l, const te_vec *f, te_vec *u, bool u_zero);
 int vcycleWith(te_gmg *g, const te_cycle_opts *o, const te_vec *f, te_vec *u, const PendingRhs *pending); // te_vcycle; `pending`: see PendingRhs
 int cycleFrom(te_gmg *g, const te_cycle_opts *o, int l, const te_vec *f, te_vec *u); // one cycle entered at level l (te_fmg)
+int verifyBeforeCycle(te_gmg *g, const te_cycle_opts *o); // sharded: placement check and, with new options, the schedule check (te_vcycle, vcycleCoef)
 
 // x-face columns of `d`, if the level still holds them (RB-GS sweeps and the single-pass patch solve produce them, inside te_vcycle)
 inline const double *xfFor(LevelHost &L, const double *d) { return (d && L.xf_valid_for == d) ? L.xfbuf[L.xf_cur].p : nullptr; }

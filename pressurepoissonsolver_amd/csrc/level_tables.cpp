@@ -439,6 +439,39 @@ int64_t layOut(const std::vector<Blk> &blks, int64_t pos, std::vector<int32_t> &
 	return pos;
 }
 
+// the same blocks with face-vector sizes (LevelTables::up_foff / down_foff): offsets from `pos` on and (peer, size) items; returns the end
+int64_t layOutFaces(const std::vector<Blk> &blks, int64_t pos, int D, int n, std::vector<int64_t> &off, PeerItems &items)
+{
+	for (auto &b : blks) {
+		const int64_t size = faceDoubles(D, b.o < 0 ? n : n / 2);
+		off.push_back(pos);
+		items.emplace_back(b.peer, size);
+		pos += size;
+	}
+	return pos;
+}
+
+// restriction towards a level that lives on every rank: the same range [0, up_total) of the send buffer to every other rank (if this
+// rank has patches here at all), and from every rank that has patches here its blocks (`downs`)
+ExPlan replicatedUpPlan(const Hierarchy &H, const PeerItems &downs, int64_t up_total)
+{
+	const ExPlan pl = mergePlan({}, downs);
+	if (up_total <= 0) return pl;
+	ExPlan full;
+	size_t k = 0;
+	for (int r = 0; r < H.nranks; r++) {
+		if (r == H.rank) continue;
+		while (k < pl.peers.size() && pl.peers[k] < r) k++;
+		const bool have = k < pl.peers.size() && pl.peers[k] == r;
+		full.peers.push_back(r);
+		full.send_off.push_back(0);
+		full.send_cnt.push_back(up_total);
+		full.recv_off.push_back(have ? pl.recv_off[k] : 0);
+		full.recv_cnt.push_back(have ? pl.recv_cnt[k] : 0);
+	}
+	return full;
+}
+
 // The coarser level cv lives on every rank and lv does not: every local patch's restricted block goes to every other rank, and
 // nothing comes back up. `downs`: the blocks this rank receives. Also: what that placement allows in 3D (post_exchange_free with
 // slot_parent / slot_orth, and the in-place exchange tx_direct).
@@ -446,25 +479,8 @@ void replicatedPlans(const Hierarchy &H, const Level &lv, const Level &cv, const
                      LevelTables &T)
 {
 	const int me = H.rank;
-	// restrict: the same range of upbuf to every other rank (if this rank has patches here at all), and from every rank
-	// that has patches here its blocks; prolong: nothing
-	T.tx_up = mergePlan({}, downs);
-	if (T.up_total > 0) {
-		const ExPlan &pl = T.tx_up;
-		ExPlan        full;
-		size_t        k = 0;
-		for (int r = 0; r < H.nranks; r++) {
-			if (r == me) continue;
-			while (k < pl.peers.size() && pl.peers[k] < r) k++;
-			const bool have = k < pl.peers.size() && pl.peers[k] == r;
-			full.peers.push_back(r);
-			full.send_off.push_back(0);
-			full.send_cnt.push_back(T.up_total);
-			full.recv_off.push_back(have ? pl.recv_off[k] : 0);
-			full.recv_cnt.push_back(have ? pl.recv_cnt[k] : 0);
-		}
-		T.tx_up = full;
-	}
+	// restrict: the same range of upbuf to every other rank, and from every rank that has patches here its blocks; prolong: nothing
+	T.tx_up = replicatedUpPlan(H, downs, T.up_total);
 	if (lv.dim != 3) return;
 	T.post_exchange_free = uniformlyRefined(lv);
 	if (T.post_exchange_free && T.nremote > 0) {
@@ -540,8 +556,9 @@ int transferTables(const Hierarchy &H, const Level &lv, const Level &cv, const L
 	}
 	std::sort(up.begin(), up.end());
 	std::sort(down.begin(), down.end());
-	PeerItems ups, downs, none;
-	T.up_total = layOut(up, 0, T.up_desc, T.up_off, ups);
+	PeerItems ups, downs, none, fups, fdowns, fnone;
+	T.up_total  = layOut(up, 0, T.up_desc, T.up_off, ups);
+	T.up_ftotal = layOutFaces(up, 0, D, n, T.up_foff, fups);
 	for (size_t i = 0; i < up.size(); i++) parent[up[i].patch] = -((int) i + 2); // prolong reads block i of upbuf
 	if (T.repl_up) { // (up is empty: every parent is local) one block per local patch, in the order the receivers expect: (parent, orthant)
 		std::vector<Blk> bc;
@@ -549,13 +566,15 @@ int transferTables(const Hierarchy &H, const Level &lv, const Level &cv, const L
 		std::sort(bc.begin(), bc.end());
 		// up_desc (fine patch, orthant): k_restrict_pack restricts it into its block; bc_desc (coarse patch, orthant or -1):
 		// k_prolong_pack copies the finished octant out
-		T.up_total = layOut(bc, T.up_total, T.up_desc, T.up_off, none);
+		T.up_total  = layOut(bc, T.up_total, T.up_desc, T.up_off, none);
+		T.up_ftotal = layOutFaces(bc, T.up_ftotal, D, n, T.up_foff, fnone);
 		for (auto &b : bc) {
 			T.bc_desc.push_back(parent[b.patch]);
 			T.bc_desc.push_back(b.o);
 		}
 	}
-	T.down_total = layOut(down, 0, T.down_desc, T.down_off, downs);
+	T.down_total  = layOut(down, 0, T.down_desc, T.down_off, downs);
+	T.down_ftotal = layOutFaces(down, 0, D, n, T.down_foff, fdowns);
 	for (size_t i = 0; i < down.size(); i++) // restrict reads block i of downbuf
 		child[(size_t) down[i].patch * NCH + std::max(down[i].o, 0)] = -((int) i + 2);
 	for (int pc = 0; pc < cv.P; pc++) {
@@ -580,9 +599,11 @@ int transferTables(const Hierarchy &H, const Level &lv, const Level &cv, const L
 	if (D == 2 && T.lds2d) T.fuse2_ok = uniformlyRefined(lv); // the 3D fusions in 2D (kernels2d.hpp): a global fact, as in 3D
 	if (T.repl_up) {
 		replicatedPlans(H, lv, cv, recvs, downs, T);
+		T.tx_fup = replicatedUpPlan(H, fdowns, T.up_ftotal);
 	} else {
 		T.tx_up   = mergePlan(ups, downs); // restrict: send child blocks, receive into downbuf
 		T.tx_down = mergePlan(downs, ups); // prolong: send octants, receive into upbuf
+		T.tx_fup  = mergePlan(fups, fdowns); // the restriction of a face vector: the same blocks with face-vector sizes
 	}
 	if (T.prolong_fusable && D == 3) { // ProlongSrc::cbase: coarseOctant() of every patch and of its six neighbours, precomputed
 		const int64_t nn = (int64_t) n * n, nnn = nn * n, hh = n / 2;

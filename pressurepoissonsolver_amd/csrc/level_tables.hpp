@@ -49,6 +49,14 @@ struct LevelTables {
 	std::vector<int64_t> up_off, down_off, cbase;
 	int64_t              up_total = 0, down_total = 0; // doubles in upbuf / downbuf
 	ExPlan               tx_up, tx_down, tx_direct;
+	// The same blocks in the same order with FACE-vector sizes (the restriction of a face vector to parents on other ranks,
+	// te_faces_restrict / te_gmg_set_coefficient): an orthant block is the face vector of a patch of n/2 cells per axis,
+	// faceDoubles(dim, n / 2) doubles, a copy-through block the patch's own faceDoubles(dim, n). up_foff[i] / down_foff[i]: where
+	// block i of up_desc / down_desc starts in the face send / receive buffer; tx_fup: children send, parents receive (under
+	// repl_up one copy to everybody, as tx_up). Nothing travels down: there is no prolongation of a face vector.
+	std::vector<int64_t> up_foff, down_foff;
+	int64_t              up_ftotal = 0, down_ftotal = 0;
+	ExPlan               tx_fup;
 	bool prolong_fusable = false, prolong_fusable_cf = false, has_copy = false, repl_up = false, repl_direct = false,
 	     post_exchange_free = false;
 	// interfaces (mesh.hpp Level::iface_*), passed through
@@ -62,6 +70,9 @@ struct LevelTables {
 	// [1 + q] of the children, q = the child's orthant bits on the face's remaining axes (the lower axis in bit 0)
 	std::vector<int32_t> brestrict;
 };
+
+/// doubles of a face vector per patch of m cells per axis: dim lower-face blocks of m^dim and dim upper-face blocks of m^(dim-1)
+inline int64_t faceDoubles(int dim, int64_t m) { return dim == 3 ? 3 * m * m * m + 3 * m * m : 2 * m * m + 2 * m; }
 
 /// fills `out` for level li of H as rank H.rank sees it; TE_OK, or an error code with te::fail's message
 int computeLevelTables(const te::Hierarchy &H, int li, const LevelBuildOpts &o, LevelTables &out);
