@@ -10,17 +10,17 @@ selected the coarsest level of the cycle, in place of its `coarse` sweeps,
 The auxiliary level-0 beta and sigma are the split of the coarsest level's: a patch's lo block is the matching block of the big lo,
 its hi the big lo plane at offset + s, or the big hi on the big patch's upper face. Below that they restrict as ever.
 
-    Sub           the auxiliary hierarchy of a one-patch level: levels, the cell offsets of its level-0 patches, split / merge
-    visit         GMG/Cycle.h:56-126 from level l on with u CARRIED (varcoef_util.cycle starts level 0 from zero), the coarsest level
-                  by sweeps or by a Sub
-    cycle / bicgstab   varcoef_util's / reaction_util's with that coarsest level; without a Sub their bits
+    Sub           the auxiliary hierarchy of a one-patch level: levels, the cell offsets of its level-0 patches, split / merge, and
+                  solve: cycle_util.visit on it with u CARRIED (varcoef_util.cycle starts level 0 from zero)
+    make_sub      the Sub of a hierarchy's coarsest level; varcoef_util.cycle / bicgstab take it as `sub=` and hand the coarsest
+                  level to its solve in place of the sweeps
 
-sigma = None means no reaction term: the functions of reaction_util with sigma = 0, which are varcoef_util's bit for bit
+sigma = None means no reaction term: varcoef_util's functions without sigma, which are those with sigma = 0 bit for bit
 (tests/test_reaction_host.py)."""
 import numpy as np
 
 from oracle import oracle as orc
-from tests import reaction_util as ru, util, varcoef_util as vc
+from tests import cycle_util, reaction_util as ru, util, varcoef_util as vc
 
 
 def valid_sub_n(dim, n, s):
@@ -98,47 +98,13 @@ class Sub:
         self.betas = vc.restrict_all(self.levels, self.split_faces(beta))
         self.sigmas = None if sigma is None else ru.restrict_all(self.levels, self.split(sigma))
 
-    def solve(self, f, u, prolong, **kw):
+    def solve(self, f, u, prolong, smoother=2, omega=6.0 / 7.0, **kw):
+        """`cycles` cycles on the auxiliary hierarchy, u CARRIED (varcoef_util.cycle starts level 0 from zero); kw: cycle_util.visit's"""
+        A, smooth = vc.operator(self.levels, self.betas, self.sigmas, smoother, omega)
         fa, ua = self.split(f), self.split(u)
         for _ in range(self.cycles):
-            ua = visit(self.levels, self.betas, self.sigmas, 0, fa, ua, prolong, **kw)
+            ua = cycle_util.visit(self.levels, 0, fa, ua, A, smooth, prolong, **kw)
         return self.merge(ua)
-
-
-def visit(levels, betas, sigmas, l, f, u, prolong, sub=None, smoother=2, pre=1, post=1, coarse=1, mid=1, cycle_type=0, omega=6.0 / 7.0):
-    """the cycle from level l on, u carried; the coarsest level: `coarse` sweeps, or sub.solve with the same options"""
-    kw = dict(smoother=smoother, pre=pre, post=post, coarse=coarse, mid=mid, cycle_type=cycle_type, omega=omega)
-    L, nl = levels[l], len(levels)
-    sig = np.zeros(L.size) if sigmas is None else sigmas[l]
-
-    def smooth(u):
-        if smoother == 1:
-            return ru.jacobi(L, betas[l], sig, f, u, omega)
-        return ru.rbgs(L, betas[l], sig, f, u)
-
-    if l == nl - 1:
-        if sub is not None:
-            return sub.solve(f, u, prolong, **kw)
-        for _ in range(coarse):
-            u = smooth(u)
-        return u
-
-    def descend(u):
-        r = -1 * ru.apply(L, betas[l], sig, u) + f
-        cf = orc.restrict(L, levels[l + 1], r)
-        cu = visit(levels, betas, sigmas, l + 1, cf, np.zeros(levels[l + 1].size), prolong, sub=sub, **kw)
-        return prolong(L, levels[l + 1], cu, u)
-
-    for _ in range(pre):
-        u = smooth(u)
-    u = descend(u)
-    if cycle_type == 1:
-        for _ in range(mid):
-            u = smooth(u)
-        u = descend(u)
-    for _ in range(post):
-        u = smooth(u)
-    return u
 
 
 def make_sub(levels, betas, sigmas, s, cycles=2):
@@ -146,37 +112,3 @@ def make_sub(levels, betas, sigmas, s, cycles=2):
     sub = Sub(levels[-1], s, cycles)
     sub.set_coefficient(betas[-1], None if sigmas is None else sigmas[-1])
     return sub
-
-
-def cycle(levels, betas, sigmas, f, prolong, sub=None, **kw):
-    return visit(levels, betas, sigmas, 0, np.ascontiguousarray(f, np.float64), np.zeros(levels[0].size), prolong, sub=sub, **kw)
-
-
-def bicgstab(levels, betas, sigmas, b, prolong, sub=None, max_it=100, tol=1e-12, **kw):
-    """varcoef_util.bicgstab / reaction_util.bicgstab, statement for statement, preconditioned by the cycle above -> (x, iterations)"""
-    L = levels[0]
-    sig = np.zeros(L.size) if sigmas is None else sigmas[0]
-    A = lambda v: ru.apply(L, betas[0], sig, v)
-    M = lambda v: cycle(levels, betas, sigmas, v, prolong, sub=sub, **kw)
-    x = np.zeros(L.size)
-    resid = -1 * A(x) + b
-    r0 = np.linalg.norm(resid)
-    rhat, p = resid.copy(), resid.copy()
-    rho = rhat @ resid
-    its = 0
-    while np.linalg.norm(resid) / r0 > tol and its < max_it:
-        mp = M(p)
-        ap = A(mp)
-        alpha = rho / (rhat @ ap)
-        s = resid + ap * -alpha
-        ms = M(s)
-        as_ = A(ms)
-        omega = (as_ @ s) / (as_ @ as_)
-        x = x + mp * alpha + ms * omega
-        resid = resid + ap * -alpha + as_ * -omega
-        rho_new = resid @ rhat
-        beta = rho_new * alpha / (rho * omega)
-        p = beta * (p + ap * -omega) + resid
-        its += 1
-        rho = rho_new
-    return x, its

@@ -1,9 +1,11 @@
 """Test infrastructure of the linear interpolator (TE_INTERP_LINEAR): the numpy statement of its semantics -- the specification
-the device kernels are held to -- and a cycle / BiCGStab composed in Python from the oracle's pieces, so that the prolongation
-can be swapped. With orc.prolong_add the composition IS orc.cycle (tests/test_prolong_host.py asserts equality to 0.0)."""
+the device kernels are held to -- and a cycle / BiCGStab composed in Python (tests/cycle_util.py's driver) from the oracle's pieces,
+so that the prolongation can be swapped. With orc.prolong_add the composition IS orc.cycle (tests/test_prolong_host.py asserts
+equality to 0.0)."""
 import numpy as np
 
 from oracle import oracle as orc
+from tests import cycle_util
 
 
 def extended(C, e):
@@ -63,9 +65,10 @@ def direct(F, C, e, u):
     return orc.prolong_add(F, C, e, u)
 
 
-def cycle(levels, f, prolong, smoother=2, pre=1, post=1, coarse=1, mid=1, cycle_type=0, omega=6.0 / 7.0, exact_coarse=1):
-    """oracle/te_oracle.cpp visit() statement by statement (GMG/Cycle.h:56-126, VCycle.h, WCycle.h), the prolongation a parameter.
-    smoother: 0 block Jacobi (exact patch solves), 1 Jacobi, 2 patch-local RB-GS -- the numbers of TE_SMOOTH_*."""
+def cycle(levels, f, prolong, smoother=2, omega=6.0 / 7.0, exact_coarse=1, **kw):
+    """oracle/te_oracle.cpp visit() statement by statement (cycle_util.visit with the oracle's operator and sweeps), the prolongation
+    a parameter. smoother: 0 block Jacobi (exact patch solves), 1 Jacobi, 2 patch-local RB-GS -- the numbers of TE_SMOOTH_*.
+    kw: pre, post, coarse, mid, cycle_type."""
     nl = len(levels)
 
     def smooth(l, f, u):
@@ -76,31 +79,7 @@ def cycle(levels, f, prolong, smoother=2, pre=1, post=1, coarse=1, mid=1, cycle_
             return orc.jacobi(L, f, u, omega)
         return orc.patch_rbgs(L, f, u)
 
-    def visit(l, f, u):
-        L = levels[l]
-        if l == nl - 1:
-            for _ in range(coarse):
-                u = smooth(l, f, u)
-            return u
-
-        def descend(u):
-            r = -1 * orc.apply(L, u) + f
-            cf = orc.restrict(L, levels[l + 1], r)
-            cu = visit(l + 1, cf, np.zeros(levels[l + 1].size))
-            return prolong(L, levels[l + 1], cu, u)
-
-        for _ in range(pre):
-            u = smooth(l, f, u)
-        u = descend(u)
-        if cycle_type == 1:
-            for _ in range(mid):
-                u = smooth(l, f, u)
-            u = descend(u)
-        for _ in range(post):
-            u = smooth(l, f, u)
-        return u
-
-    return visit(0, np.ascontiguousarray(f, np.float64), np.zeros(levels[0].size))
+    return cycle_util.cycle(levels, f, lambda l, u: orc.apply(levels[l], u), smooth, prolong, **kw)
 
 
 def reductions(levels, f, prolong, cycles=8, **kw):
@@ -119,27 +98,4 @@ def reductions(levels, f, prolong, cycles=8, **kw):
 
 def bicgstab(levels, b, prolong, max_it=100, tol=1e-12, **kw):
     """oracle/te_oracle.cpp orc_bicgstab (BiCGStab.h:45-106), right-preconditioned by the composed cycle -> (x, iterations)"""
-    L = levels[0]
-    M = lambda v: cycle(levels, v, prolong, **kw)
-    x = np.zeros(L.size)
-    resid = -1 * orc.apply(L, x) + b
-    r0 = np.linalg.norm(resid)
-    rhat, p = resid.copy(), resid.copy()
-    rho = rhat @ resid
-    its = 0
-    while np.linalg.norm(resid) / r0 > tol and its < max_it:
-        mp = M(p)
-        ap = orc.apply(L, mp)
-        alpha = rho / (rhat @ ap)
-        s = resid + ap * -alpha
-        ms = M(s)
-        as_ = orc.apply(L, ms)
-        omega = (as_ @ s) / (as_ @ as_)
-        x = x + mp * alpha + ms * omega
-        resid = resid + ap * -alpha + as_ * -omega
-        rho_new = resid @ rhat
-        beta = rho_new * alpha / (rho * omega)
-        p = beta * (p + ap * -omega) + resid
-        its += 1
-        rho = rho_new
-    return x, its
+    return cycle_util.bicgstab(lambda v: orc.apply(levels[0], v), lambda v: cycle(levels, v, prolong, **kw), b, max_it, tol)

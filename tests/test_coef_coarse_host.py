@@ -13,7 +13,7 @@ import functools
 import numpy as np
 import pytest
 
-from tests import coefcoarse_util as cu, prolong_util, reaction_util as ru, util, varcoef_util as vc
+from tests import coefcoarse_util as cu, prolong_util, util, varcoef_util as vc
 
 # (mesh, n, divides, dim): the hierarchies of the table; their coarsest levels are one patch of 8^3, 16^2, 16^2, 16^3, 32^2
 SHAPES = [("uniform", 8, 1, 3), ("uniform", 16, 2, 2), ("2d2ref.bin", 16, 0, 2), ("uniform", 16, 1, 3), ("uniform", 32, 1, 2)]
@@ -35,11 +35,6 @@ def setup(name, n, div, dim):
     return H, levels
 
 
-def random_beta(L, seed):
-    rng = np.random.default_rng(seed)
-    return rng.uniform(0.5, 2.0, (L.P, L.dim) + (L.n,) * L.dim), rng.uniform(0.5, 2.0, (L.P, L.dim) + (L.n,) * (L.dim - 1))
-
-
 @pytest.mark.parametrize("name,n,div,dim", SHAPES, ids=lambda v: str(v))
 def test_split_then_merge_is_the_identity(name, n, div, dim):
     H, levels = setup(name, n, div, dim)
@@ -51,7 +46,7 @@ def test_split_then_merge_is_the_identity(name, n, div, dim):
     assert np.array_equal(sub.merge(w), v)
     assert np.array_equal(sub.split(sub.merge(w)), w)
     # the split beta: a shared face has equal copies, a face on the big patch's boundary is the big patch's
-    beta = random_beta(big, 2)
+    beta = vc.random_beta_faces(big, 2)
     lo, hi = sub.split_faces(beta)
     A, shared = sub.levels[0], 0
     for q in range(A.P):
@@ -73,7 +68,7 @@ def test_split_then_merge_is_the_identity(name, n, div, dim):
 def test_the_operator_on_the_split_tree_is_the_operator_on_the_patch(name, n, div, dim):
     H, levels = setup(name, n, div, dim)
     big = levels[-1]
-    beta = random_beta(big, 3)
+    beta = vc.random_beta_faces(big, 3)
     sigma = np.random.default_rng(4).uniform(0.0, 50.0, big.size)
     for s in [c for c in (4, 8) if cu.valid_sub_n(dim, n, c)]:
         sub = cu.Sub(big, s)
@@ -82,17 +77,18 @@ def test_the_operator_on_the_split_tree_is_the_operator_on_the_patch(name, n, di
         diff = np.abs(vc.apply(sub.levels[0], sub.betas[0], sub.split(u)) - sub.split(vc.apply(big, beta, u))).max()
         print(f"A_b on the split tree against the patch, sub_n {s}: max difference {diff}")
         assert diff == 0, s
-        diff = np.abs(ru.apply(sub.levels[0], sub.betas[0], sub.sigmas[0], sub.split(u)) - sub.split(ru.apply(big, beta, sigma, u))).max()
+        diff = np.abs(vc.apply(sub.levels[0], sub.betas[0], sub.split(u), sub.sigmas[0]) - sub.split(vc.apply(big, beta, u, sigma))).max()
         print(f"A_b,sigma: max difference {diff}")
         assert diff == 0, s
 
 
 def test_without_a_sub_cycle_the_composition_is_varcoef_utils():
     H, levels = setup("uniform", 8, 1, 3)
-    betas = vc.restrict_all(levels, random_beta(levels[0], 6))
+    betas = vc.restrict_all(levels, vc.random_beta_faces(levels[0], 6))
     f = util.rand_vec(levels[0].size, 7)
+    zeros = [np.zeros(L.size) for L in levels]  # "no reaction term" as sigma = 0 on every level: the bits of sigmas=None
     for kw in (dict(coarse=4), dict(smoother=1, coarse=3, cycle_type=1)):
-        assert np.array_equal(cu.cycle(levels, betas, None, f, prolong_util.direct, **kw), vc.cycle(levels, betas, f, prolong_util.direct, **kw)), kw
+        assert np.array_equal(vc.cycle(levels, betas, f, prolong_util.direct, sigmas=zeros, sub=None, **kw), vc.cycle(levels, betas, f, prolong_util.direct, **kw)), kw
 
 
 def test_sub_n_rule():
@@ -111,7 +107,7 @@ def test_iteration_table(name, n, div, dim, beta_fn):
     got = []
     for label, cycles, coarse in COLUMNS:
         sub = None if cycles is None else cu.make_sub(levels, betas, None, 4, cycles)
-        x, its = cu.bicgstab(levels, betas, None, b, prolong_util.direct, sub=sub, tol=1e-10, coarse=coarse)
+        x, its = vc.bicgstab(levels, betas, b, prolong_util.direct, sub=sub, tol=1e-10, coarse=coarse)
         assert np.linalg.norm(b - vc.apply(levels[0], betas[0], x)) <= 1e-9 * np.linalg.norm(b), label
         got.append(its)
     want = [col[beta_fn is vc.jump_beta] for col in TABLE[(name, n, div, dim)]]

@@ -19,7 +19,7 @@ import pytest
 
 from pressurepoissonsolver_amd import capi
 from tests import bc_util, coefcoarse_util as cu, projection_util as pu, prolong_util, reaction_util as ru, util, varcoef_util as vc
-from tests.test_gpu_varcoef import masks_of, rel
+from tests.varcoef_util import masks_of, random_beta_faces as random_beta, refused, rel, solve_setup
 
 pytestmark = pytest.mark.gpu
 
@@ -27,11 +27,6 @@ SUB, SWEEPS = capi.COEF_COARSE_SUBCYCLE, capi.COEF_COARSE_SWEEPS
 # (dim, n, sub_n): one and two refinements of every 3D sub-patch kernel size that fits, three refinements of 4^3 patches (the Morton
 # order of the offset table), 2D with two and three refinements
 ONE_LEVEL = [(3, 8, 4), (3, 16, 4), (3, 32, 8), (3, 32, 4), (2, 16, 4), (2, 64, 8)]
-
-
-def random_beta(L, seed):
-    rng = np.random.default_rng(seed)
-    return rng.uniform(0.5, 2.0, (L.P, L.dim) + (L.n,) * L.dim), rng.uniform(0.5, 2.0, (L.P, L.dim) + (L.n,) * (L.dim - 1))
 
 
 class Composed:
@@ -138,12 +133,6 @@ def test_one_level_hierarchies_bit_for_bit(dim, n, s, kind, with_sigma):
 INSIDE = [("uniform", 8, 1, 3), ("2refine.bin", 8, 0, 3), ("uniform", 16, 2, 2), ("2d2ref.bin", 16, 0, 2)]
 
 
-@functools.lru_cache(maxsize=None)
-def solve_setup(name, n, div, dim):
-    m, H, levels = util.setup(name, n, div, dim=dim)
-    return H, levels, capi.GMG(H)
-
-
 @pytest.mark.parametrize("interp", [capi.INTERP_DIRECT, capi.INTERP_LINEAR], ids=["direct", "linear"])
 @pytest.mark.parametrize("with_sigma", [False, True], ids=["beta", "beta+sigma100"])
 @pytest.mark.parametrize("beta_fn", [vc.smooth_beta, vc.jump_beta], ids=["smooth", "jump"])
@@ -166,10 +155,10 @@ def test_cycle_and_solve_against_the_cpu_composition(name, n, div, dim, beta_fn,
         o = g.default_opts(smoother=capi.SMOOTH_RBGS, coarse_sweeps=8)
         db, du = g.new_vector(0, b), g.new_vector(0)
         g.cycle(o, db, du)
-        err = rel(du.download(), cu.cycle(levels, betas, sigmas, b, prolong, sub=sub, coarse=8))
+        err = rel(du.download(), vc.cycle(levels, betas, b, prolong, sigmas=sigmas, sub=sub, coarse=8))
         print(f"cycle: {err:.3e}")
         assert err <= 1e-10
-        x_ref, its_ref = cu.bicgstab(levels, betas, sigmas, b, prolong, sub=sub, tol=1e-10, coarse=8)
+        x_ref, its_ref = vc.bicgstab(levels, betas, b, prolong, sigmas=sigmas, sub=sub, tol=1e-10, coarse=8)
         dx = g.new_vector(0)
         its, rr = g.bicgstab(dx, db, o, tol=1e-10, max_it=40)
         print(f"solve: {its} iterations on the device, {its_ref} in the composition, relative residual {rr:.2e}")
@@ -271,14 +260,6 @@ def test_without_a_coefficient_nothing_changes():
     g.set_coef_coarse(SWEEPS)
     g.cycle(g.default_opts(), f, u)
     assert u.checksumLocal() == before
-
-
-def refused(call, code, word=None):
-    with pytest.raises(capi.TeError) as e:
-        call()
-    assert e.value.code == code, str(e.value)
-    if word is not None:
-        assert word in str(e.value), str(e.value)
 
 
 def test_refusals():

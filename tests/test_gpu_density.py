@@ -235,22 +235,11 @@ def test_weighted_fold(key):
 
 
 # ---- the whole step: rho as a cell vector -> beta -> solve -> divergence-free face velocity
-def manufactured3d():
-    """beta = exp(x + y + z), u = sin(2x + 0.3) sin(3y + 0.1) sin(1.5z + 0.2), F = div(beta grad u)"""
-    beta = lambda x, y, z: np.exp(x + y + z)
-    sx, sy, sz = (lambda x: np.sin(2 * x + 0.3)), (lambda y: np.sin(3 * y + 0.1)), (lambda z: np.sin(1.5 * z + 0.2))
-    cx, cy, cz = (lambda x: np.cos(2 * x + 0.3)), (lambda y: np.cos(3 * y + 0.1)), (lambda z: np.cos(1.5 * z + 0.2))
-    u = lambda x, y, z: sx(x) * sy(y) * sz(z)
-    F = lambda x, y, z: np.exp(x + y + z) * (-(4 + 9 + 2.25) * u(x, y, z) + 2 * cx(x) * sy(y) * sz(z) + 3 * sx(x) * cy(y) * sz(z)
-                                             + 1.5 * sx(x) * sy(y) * cz(z))
-    return beta, u, F
-
-
 @pytest.mark.parametrize("name,n,div,dim", [("uniform", 8, 3, 2), ("uniform", 8, 2, 3), ("2refine.bin", 8, 0, 3)], ids=["2d", "3d", "3d-refined"])
 def test_the_whole_step_stays_on_the_device(name, n, div, dim):
     m, H, levels = util.setup(name, n, div, dim=dim)
     g, L, t = capi.GMG(H), levels[0], H.tables(0)
-    beta_fn, u_fn, F_fn = vc.manufactured2d() if dim == 2 else manufactured3d()
+    beta_fn, u_fn, F_fn = vc.manufactured2d() if dim == 2 else vc.manufactured3d()
     at = lambda fn, pts: fn(*[pts[:, b] for b in range(dim)])
     cc = vc.cell_centres(t, n, dim)
     cells = np.concatenate([np.stack([cc[p, b].ravel() for b in range(dim)], axis=1) for p in range(L.P)])

@@ -1,5 +1,6 @@
 """-m gpu: the reaction term A_bs u = div(beta grad u) - sigma u (include/te_hip.h te_gmg_set_reaction and what follows it) against the
-numpy statement of tests/reaction_util.py, which tests/test_reaction_host.py pins to varcoef_util's and the oracle.
+numpy statement of tests/varcoef_util.py with sigma (tests/reaction_util.py holds what is sigma's own), which tests/test_reaction_host.py
+pins to the statement without sigma and the oracle.
 
 Bounds (none of them comes from what the kernels give):
   apply / residual   max(beta) * util.op_tol(u) + 4 eps max(sigma) max|u|: section 18's bound plus one multiplication and one subtraction
@@ -11,59 +12,18 @@ Bounds (none of them comes from what the kernels give):
   cycle / solve      1e-10 relative; iteration count +-1 and 1e-8 relative: the conventions of test_gpu_parity.py
   manufactured       solve to 1e-12 within 1e-8 relative of the CPU composition's, error against the exact u within 1 % of its error"""
 import contextlib
-import functools
 
 import numpy as np
 import pytest
 
 from pressurepoissonsolver_amd import capi
 from tests import bc_util, projection_util as pu, prolong_util, reaction_util as ru, util, varcoef_util as vc
+from tests.reaction_util import device_sigmas, random_sigma
+from tests.varcoef_util import CASES, SOLVES, device_betas, random_beta, refused, rel, solve_setup
 
 pytestmark = pytest.mark.gpu
 
-# (mesh, divides, n, dim): the shapes of test_gpu_varcoef.py, for its reasons: whole-patch path; smallest tile; 8 patches of the
-# production tile; coarse/fine ghosts and copy-through; 2D; 2D refined; the largest 2D patch the LDS form of the sweep takes
-SHAPES = [("uniform", 2, 8, 3), ("uniform", 1, 4, 3), ("uniform", 1, 32, 3), ("2refine.bin", 1, 8, 3), ("uniform", 3, 8, 2), ("2d2ref.bin", 2, 8, 2),
-          ("uniform", 1, 64, 2)]
 OMEGA = 6.0 / 7.0
-
-
-def masks_of(dim):
-    return (0, (1 << 2 * dim) - 1, bc_util.CHANNEL if dim == 3 else bc_util.MASKS2[0])  # Dirichlet, all-Neumann, mixed
-
-
-CASES = [s + (mask,) for s in SHAPES for mask in masks_of(s[3])]
-
-
-def rel(a, b):
-    return np.linalg.norm(a - b) / np.linalg.norm(b)
-
-
-def random_beta(size, seed):
-    return np.random.default_rng(seed).uniform(0.5, 2.0, size)
-
-
-def random_sigma(size, seed):
-    """a spread this wide makes a sigma read at the wrong cell or plane show"""
-    return np.random.default_rng(seed).uniform(0.0, 50.0, size)
-
-
-def device_betas(g, levels, n, dim):
-    out = []
-    for l in range(len(levels)):
-        v = g.new_face_vector(l)
-        g.coefficient(l, v)
-        out.append(pu.unpack(v.download(), n, dim))
-    return out
-
-
-def device_sigmas(g, levels):
-    out = []
-    for l in range(len(levels)):
-        v = g.new_vector(l)
-        g.reaction(l, v)
-        out.append(v.download())
-    return out
 
 
 def op_bound(L, beta, sigma, u):
@@ -91,7 +51,7 @@ def test_apply_and_residual(case):
         u, f = util.rand_vec(L.size, 100 + l), util.rand_vec(L.size, 110 + l)
         du, df, dA, dr = g.new_vector(l, u), g.new_vector(l, f), g.new_vector(l), g.new_vector(l)
         g.apply(du, dA, level=l)
-        A, want = dA.download(), ru.apply(L, beta, sigma, u)
+        A, want = dA.download(), vc.apply(L, beta, u, sigma)
         tol = op_bound(L, beta, sigma, u)
         err = np.abs(A - want).max()
         print(f"apply level {l}: {err / tol:.3f} of the bound")
@@ -112,7 +72,7 @@ def test_one_sweep(case):
     for l, L in enumerate(case["levels"]):
         beta, sigma = case["betas"][l], case["sigmas"][l]
         u, f = util.rand_vec(L.size, 120 + l), util.rand_vec(L.size, 130 + l)
-        for sm, want in ((capi.SMOOTH_RBGS, ru.rbgs(L, beta, sigma, f, u)), (capi.SMOOTH_JACOBI, ru.jacobi(L, beta, sigma, f, u, OMEGA))):
+        for sm, want in ((capi.SMOOTH_RBGS, vc.rbgs(L, beta, f, u, sigma)), (capi.SMOOTH_JACOBI, vc.jacobi(L, beta, f, u, OMEGA, sigma))):
             du, df = g.new_vector(l, u), g.new_vector(l, f)
             g.smooth(df, du, level=l, smoother=sm, omega=OMEGA)
             err = rel(du.download(), want)
@@ -132,7 +92,7 @@ def test_sweep_above_the_lds_limit():
         u, f = util.rand_vec(L.size, 120 + l), util.rand_vec(L.size, 130 + l)
         du, df = g.new_vector(l, u), g.new_vector(l, f)
         g.smooth(df, du, level=l, smoother=capi.SMOOTH_RBGS)
-        err = rel(du.download(), ru.rbgs(L, betas[l], sigmas[l], f, u))
+        err = rel(du.download(), vc.rbgs(L, betas[l], f, u, sigmas[l]))
         print(f"128^2 sweep level {l}: {err:.3e}")
         assert err <= 1e-11, l
 
@@ -184,7 +144,7 @@ def test_slab_matrix(n):
     g.set_reaction(g.new_vector(0, random_sigma(levels[0].size, 17)))
     betas, sigmas = device_betas(g, levels, n, 3), device_sigmas(g, levels)
     inputs = [(util.rand_vec(L.size, 100 + l), util.rand_vec(L.size, 110 + l)) for l, L in enumerate(levels)]
-    refs = [(ru.apply(L, betas[l], sigmas[l], u), ru.rbgs(L, betas[l], sigmas[l], f, u), ru.jacobi(L, betas[l], sigmas[l], f, u, OMEGA))
+    refs = [(vc.apply(L, betas[l], u, sigmas[l]), vc.rbgs(L, betas[l], f, u, sigmas[l]), vc.jacobi(L, betas[l], f, u, OMEGA, sigmas[l]))
             for l, (L, (u, f)) in enumerate(zip(levels, inputs))]
     base = None
     for zs in COUNTS[n]:
@@ -274,16 +234,7 @@ def test_sigma_zero_and_clearing(name, n, div, dim):
     assert np.array_equal(u.download(), constant)
 
 
-# ---- against the CPU composition: the meshes of tests/test_reaction_host.py
-SOLVES = [("uniform", 8, 3, 2), ("2d2ref.bin", 8, 1, 2), ("uniform", 4, 2, 3), ("2refine.bin", 4, 0, 3)]
-
-
-@functools.lru_cache(maxsize=None)
-def solve_setup(name, n, div, dim):
-    m, H, levels = util.setup(name, n, div, dim=dim)
-    return H, levels, capi.GMG(H)
-
-
+# ---- against the CPU composition: the meshes of tests/test_reaction_host.py (varcoef_util.SOLVES)
 @pytest.mark.parametrize("interp", [capi.INTERP_DIRECT, capi.INTERP_LINEAR], ids=["direct", "linear"])
 @pytest.mark.parametrize("beta_fn", [vc.smooth_beta, vc.jump_beta], ids=["smooth", "jump"])
 @pytest.mark.parametrize("name,n,div,dim", SOLVES, ids=lambda v: str(v))
@@ -303,10 +254,10 @@ def test_cycle_and_solve_against_the_cpu_composition(name, n, div, dim, beta_fn,
         o = g.default_opts(smoother=capi.SMOOTH_RBGS, coarse_sweeps=coarse)
         db, du = g.new_vector(0, b), g.new_vector(0)
         g.cycle(o, db, du)
-        err = rel(du.download(), ru.cycle(levels, betas, sigmas, b, prolong, coarse=coarse))
+        err = rel(du.download(), vc.cycle(levels, betas, b, prolong, sigmas=sigmas, coarse=coarse))
         print(f"cycle: {err:.3e}")
         assert err <= 1e-10
-        x_ref, its_ref = ru.bicgstab(levels, betas, sigmas, b, prolong, tol=1e-10, coarse=coarse)
+        x_ref, its_ref = vc.bicgstab(levels, betas, b, prolong, tol=1e-10, sigmas=sigmas, coarse=coarse)
         dx = g.new_vector(0)
         its, rr = g.bicgstab(dx, db, o, tol=1e-10, max_it=40)
         print(f"solve: {its} iterations on the device, {its_ref} in the composition, relative residual {rr:.2e}")
@@ -330,7 +281,7 @@ def test_jacobi_and_w_cycles_against_the_cpu_composition(cycle_type):
         db, du = g.new_vector(0, b), g.new_vector(0)
         for sm in (capi.SMOOTH_JACOBI, capi.SMOOTH_RBGS):
             g.cycle(g.default_opts(smoother=sm, cycle_type=cycle_type, coarse_sweeps=4), db, du)
-            err = rel(du.download(), ru.cycle(levels, betas, sigmas, b, prolong_util.direct, smoother=sm, cycle_type=cycle_type, coarse=4))
+            err = rel(du.download(), vc.cycle(levels, betas, b, prolong_util.direct, sigmas=sigmas, smoother=sm, cycle_type=cycle_type, coarse=4))
             print(f"cycle type {cycle_type} smoother {sm}: {err:.3e}")
             assert err <= 1e-10
     finally:
@@ -342,7 +293,7 @@ def test_manufactured_implicit_diffusion_step(name, n, div, dim):
     H, levels, g = solve_setup(name, n, div, dim)
     betas, sigmas, rhs, exact = ru.manufactured_problem(H, levels, n, dim, *(ru.manufactured2d() if dim == 2 else ru.manufactured3d()))
     coarse = 32 if dim == 2 else 16
-    x_ref, _ = ru.bicgstab(levels, betas, sigmas, rhs, prolong_util.direct, tol=1e-12, coarse=coarse)
+    x_ref, _ = vc.bicgstab(levels, betas, rhs, prolong_util.direct, tol=1e-12, sigmas=sigmas, coarse=coarse)
     try:
         g.set_coefficient(g.new_face_vector(0, pu.pack(*betas[0])))
         g.set_reaction(g.new_vector(0, sigmas[0]))
@@ -393,20 +344,13 @@ def test_refusals_and_argument_checks():
     assert e.value.code == capi.TE_EINVAL
     g.set_reaction(sigma)
     gam = g.new_iface_vector(0)
-    refused = [lambda: g.fmg(f, u, g.default_opts()), lambda: g.patch_apply(u, r), lambda: g.iface_interp(u, gam),
-               lambda: g.apply_with_interface(u, gam, r), lambda: g.add_iface_rhs(gam, r), lambda: g.solve_with_interface(f, u, gam),
-               lambda: g.schur_apply(gam, g.new_iface_vector(0)), lambda: g.schur_cheb(gam, g.new_iface_vector(0)), lambda: g.schur_solve(f, u, gam)]
-    for k, call in enumerate(refused):
-        with pytest.raises(capi.TeError) as e:
-            call()
-        assert e.value.code == capi.TE_ESTATE and "coefficient" in str(e.value), (k, str(e.value))
+    for call in (lambda: g.fmg(f, u, g.default_opts()), lambda: g.patch_apply(u, r), lambda: g.iface_interp(u, gam),
+                 lambda: g.apply_with_interface(u, gam, r), lambda: g.add_iface_rhs(gam, r), lambda: g.solve_with_interface(f, u, gam),
+                 lambda: g.schur_apply(gam, g.new_iface_vector(0)), lambda: g.schur_cheb(gam, g.new_iface_vector(0)), lambda: g.schur_solve(f, u, gam)):
+        refused(call, capi.TE_ESTATE, "coefficient")
     for sm in (capi.SMOOTH_PATCH_SOLVE, capi.SMOOTH_PATCH_BCGS):
-        with pytest.raises(capi.TeError) as e:
-            g.smooth(f, u, smoother=sm)
-        assert e.value.code == capi.TE_EUNSUPPORTED
-        with pytest.raises(capi.TeError) as e:
-            g.cycle(g.default_opts(smoother=sm), f, u)
-        assert e.value.code == capi.TE_EUNSUPPORTED
+        refused(lambda: g.smooth(f, u, smoother=sm), capi.TE_EUNSUPPORTED)
+        refused(lambda: g.cycle(g.default_opts(smoother=sm), f, u), capi.TE_EUNSUPPORTED)
     # beta = 1 and a constant sigma: Laplace(u) - sigma u, the recipe of the header
     A, lap = g.new_vector(0), g.new_vector(0)
     g.apply(f, A)

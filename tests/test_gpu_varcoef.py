@@ -10,46 +10,14 @@ Bounds (none of them comes from what the kernels give):
   restriction        4 eps max|beta| (two additions and a multiplication by a power of two per entry); copy-through bit for bit
   cycle / solve      1e-10 relative; iteration count +-1 and 1e-8 relative: the conventions of test_gpu_parity.py
   end to end         max|div U| <= max|f - A_b p| + 2 max(beta) op_tol(p) + 4 eps (2 dim / h_min) max|U*|"""
-import functools
-
 import numpy as np
 import pytest
 
 from pressurepoissonsolver_amd import capi
 from tests import bc_util, projection_util as pu, prolong_util, util, varcoef_util as vc
+from tests.varcoef_util import CASES, SOLVES, device_betas, random_beta, refused, rel, solve_setup
 
 pytestmark = pytest.mark.gpu
-
-# (mesh, divides, n, dim): whole-patch path; smallest tile; 8 patches of the production tile; coarse/fine ghosts and copy-through;
-# 2D; 2D refined; the largest 2D patch the LDS form of the sweep takes (test_sweep_above_the_lds_limit: the form above it)
-SHAPES = [("uniform", 2, 8, 3), ("uniform", 1, 4, 3), ("uniform", 1, 32, 3), ("2refine.bin", 1, 8, 3), ("uniform", 3, 8, 2), ("2d2ref.bin", 2, 8, 2),
-          ("uniform", 1, 64, 2)]
-
-
-def masks_of(dim):
-    return (0, (1 << 2 * dim) - 1, bc_util.CHANNEL if dim == 3 else bc_util.MASKS2[0])  # Dirichlet, all-Neumann, mixed
-
-
-CASES = [s + (mask,) for s in SHAPES for mask in masks_of(s[3])]
-
-
-def rel(a, b):
-    return np.linalg.norm(a - b) / np.linalg.norm(b)
-
-
-def random_beta(size, seed):
-    return np.random.default_rng(seed).uniform(0.5, 2.0, size)
-
-
-def device_betas(g, levels, n, dim):
-    """the solver's coefficient on every level, downloaded -> [(lo, hi)]"""
-    out = []
-    for l in range(len(levels)):
-        v = g.new_face_vector(l)
-        g.coefficient(l, v)
-        out.append(pu.unpack(v.download(), n, dim))
-    return out
-
 
 @pytest.fixture(scope="module", params=CASES, ids=lambda c: f"{c[0]}-d{c[1]}-n{c[2]}-{c[3]}d-{c[4]:06b}")
 def case(request):
@@ -182,16 +150,7 @@ def test_beta_two_is_the_constant_coefficient_cycle(case, sm, cycle_type, interp
         g.set_coefficient(g.new_face_vector(0, case["beta0"]))
 
 
-# ---- against the CPU composition: the meshes of tests/test_varcoef_host.py
-SOLVES = [("uniform", 8, 3, 2), ("2d2ref.bin", 8, 1, 2), ("uniform", 4, 2, 3), ("2refine.bin", 4, 0, 3)]
-
-
-@functools.lru_cache(maxsize=None)
-def solve_setup(name, n, div, dim):
-    m, H, levels = util.setup(name, n, div, dim=dim)
-    return H, levels, capi.GMG(H)
-
-
+# ---- against the CPU composition: the meshes of tests/test_varcoef_host.py (varcoef_util.SOLVES)
 @pytest.mark.parametrize("interp", [capi.INTERP_DIRECT, capi.INTERP_LINEAR], ids=["direct", "linear"])
 @pytest.mark.parametrize("beta_fn", [vc.smooth_beta, vc.jump_beta], ids=["smooth", "jump"])
 @pytest.mark.parametrize("name,n,div,dim", SOLVES, ids=lambda v: str(v))
@@ -223,21 +182,11 @@ def test_cycle_and_solve_against_the_cpu_composition(name, n, div, dim, beta_fn,
         g.set_coefficient(None)
 
 
-def manufactured3d():
-    beta = lambda x, y, z: np.exp(x + y + z)
-    sx, sy, sz = (lambda x: np.sin(2 * x + 0.3)), (lambda y: np.sin(3 * y + 0.1)), (lambda z: np.sin(1.5 * z + 0.2))
-    cx, cy, cz = (lambda x: np.cos(2 * x + 0.3)), (lambda y: np.cos(3 * y + 0.1)), (lambda z: np.cos(1.5 * z + 0.2))
-    u = lambda x, y, z: sx(x) * sy(y) * sz(z)
-    F = lambda x, y, z: np.exp(x + y + z) * (-(4 + 9 + 2.25) * u(x, y, z) + 2 * cx(x) * sy(y) * sz(z) + 3 * sx(x) * cy(y) * sz(z)
-                                             + 1.5 * sx(x) * sy(y) * cz(z))
-    return beta, u, F
-
-
 @pytest.mark.parametrize("name,n,div,dim", [("uniform", 8, 3, 2), ("uniform", 8, 2, 3)], ids=["2d", "3d"])
 def test_manufactured_solve_and_projection(name, n, div, dim):
     H, levels, g = solve_setup(name, n, div, dim)
     L = levels[0]
-    betas, rhs, exact = vc.manufactured_problem(H, levels, n, dim, *(vc.manufactured2d() if dim == 2 else manufactured3d()))
+    betas, rhs, exact = vc.manufactured_problem(H, levels, n, dim, *(vc.manufactured2d() if dim == 2 else vc.manufactured3d()))
     coarse = 32 if dim == 2 else 16
     x_ref, _ = vc.bicgstab(levels, betas, rhs, prolong_util.direct, tol=1e-12, coarse=coarse)
     dbeta = g.new_face_vector(0, pu.pack(*betas[0]))
@@ -309,20 +258,13 @@ def test_calls_without_a_variable_coefficient_form_are_refused():
     assert e.value.code == capi.TE_EINVAL
     g.set_coefficient(beta)
     gam = g.new_iface_vector(0)
-    refused = [lambda: g.fmg(f, u, g.default_opts()), lambda: g.patch_apply(u, r), lambda: g.iface_interp(u, gam),
-               lambda: g.apply_with_interface(u, gam, r), lambda: g.add_iface_rhs(gam, r), lambda: g.solve_with_interface(f, u, gam),
-               lambda: g.schur_apply(gam, g.new_iface_vector(0)), lambda: g.schur_cheb(gam, g.new_iface_vector(0)), lambda: g.schur_solve(f, u, gam)]
-    for k, call in enumerate(refused):
-        with pytest.raises(capi.TeError) as e:
-            call()
-        assert e.value.code == capi.TE_ESTATE and "coefficient" in str(e.value), (k, str(e.value))
+    for call in (lambda: g.fmg(f, u, g.default_opts()), lambda: g.patch_apply(u, r), lambda: g.iface_interp(u, gam),
+                 lambda: g.apply_with_interface(u, gam, r), lambda: g.add_iface_rhs(gam, r), lambda: g.solve_with_interface(f, u, gam),
+                 lambda: g.schur_apply(gam, g.new_iface_vector(0)), lambda: g.schur_cheb(gam, g.new_iface_vector(0)), lambda: g.schur_solve(f, u, gam)):
+        refused(call, capi.TE_ESTATE, "coefficient")
     for sm in (capi.SMOOTH_PATCH_SOLVE, capi.SMOOTH_PATCH_BCGS):
-        with pytest.raises(capi.TeError) as e:
-            g.smooth(f, u, smoother=sm)
-        assert e.value.code == capi.TE_EUNSUPPORTED
-        with pytest.raises(capi.TeError) as e:
-            g.cycle(g.default_opts(smoother=sm), f, u)
-        assert e.value.code == capi.TE_EUNSUPPORTED
+        refused(lambda: g.smooth(f, u, smoother=sm), capi.TE_EUNSUPPORTED)
+        refused(lambda: g.cycle(g.default_opts(smoother=sm), f, u), capi.TE_EUNSUPPORTED)
     # te_gmg_release_workspace while a coefficient is set keeps the per-level copies: the operator does not change
     A0, A1, chk = g.new_vector(0), g.new_vector(0), g.new_face_vector(g.num_levels - 1)
     g.apply(f, A0)

@@ -1,5 +1,6 @@
-"""CPU: the numpy statement of the reaction term A_bs u = div(beta grad u) - sigma u (tests/reaction_util.py, the specification of
-te_gmg_set_reaction's path) on its own: with sigma = 0 it is varcoef_util's statement bit for bit, sigma goes down the levels by the
+"""CPU: the numpy statement of the reaction term A_bs u = div(beta grad u) - sigma u (tests/varcoef_util.py with `sigma=`, and
+tests/reaction_util.py: the specification of te_gmg_set_reaction's path) on its own: with sigma = 0 it is the statement without sigma
+(`sigma=None`: the `- sigma u` and `d + sigma` statements are not executed) bit for bit, sigma goes down the levels by the
 oracle's restriction, the discretisation stays second order, a larger diagonal does not cost iterations, and the all-Neumann problem
 is nonsingular.
 
@@ -16,13 +17,9 @@ import pytest
 
 from oracle import oracle as orc
 from tests import bc_util, prolong_util, reaction_util as ru, util, varcoef_util as vc
+from tests.varcoef_util import SOLVES
 
 ZERO_MESHES = [("uniform", 8, 2, 2), ("2d2ref.bin", 8, 1, 2), ("uniform", 4, 1, 3), ("2refine.bin", 4, 0, 3)]
-
-
-def random_beta(L, seed):
-    rng = np.random.default_rng(seed)
-    return rng.uniform(0.5, 2.0, (L.P, L.dim) + (L.n,) * L.dim), rng.uniform(0.5, 2.0, (L.P, L.dim) + (L.n,) * (L.dim - 1))
 
 
 @pytest.mark.parametrize("mask_kind", ["dirichlet", "mixed"])
@@ -30,17 +27,17 @@ def random_beta(L, seed):
 def test_sigma_zero_changes_nothing(name, n, div, dim, mask_kind):
     mask = 0 if mask_kind == "dirichlet" else (bc_util.CHANNEL if dim == 3 else bc_util.MASKS2[0])
     m, H, levels = bc_util.setup(name, n, div, mask, dim)
-    betas = vc.restrict_all(levels, random_beta(levels[0], 7))
+    betas = vc.restrict_all(levels, vc.random_beta_faces(levels[0], 7))
     zeros = [np.zeros(L.size) for L in levels]
     omega = 6.0 / 7.0
     for l, L in enumerate(levels):
         u, f = util.rand_vec(L.size, 10 + l), util.rand_vec(L.size, 20 + l)
-        assert np.array_equal(ru.apply(L, betas[l], zeros[l], u), vc.apply(L, betas[l], u)), l
-        assert np.array_equal(ru.rbgs(L, betas[l], zeros[l], f, u), vc.rbgs(L, betas[l], f, u)), l
-        assert np.array_equal(ru.jacobi(L, betas[l], zeros[l], f, u, omega), vc.jacobi(L, betas[l], f, u, omega)), l
+        assert np.array_equal(vc.apply(L, betas[l], u, zeros[l]), vc.apply(L, betas[l], u)), l
+        assert np.array_equal(vc.rbgs(L, betas[l], f, u, zeros[l]), vc.rbgs(L, betas[l], f, u)), l
+        assert np.array_equal(vc.jacobi(L, betas[l], f, u, omega, zeros[l]), vc.jacobi(L, betas[l], f, u, omega)), l
     f = util.rand_vec(levels[0].size, 30)
     for kw in (dict(smoother=2, coarse=4), dict(smoother=1, coarse=4, cycle_type=1)):
-        got = ru.cycle(levels, betas, zeros, f, prolong_util.direct, **kw)
+        got = vc.cycle(levels, betas, f, prolong_util.direct, sigmas=zeros, **kw)
         assert np.array_equal(got, vc.cycle(levels, betas, f, prolong_util.direct, **kw)), kw
 
 
@@ -69,7 +66,7 @@ def solve_errors(name, div, n=8, dim=2):
     """max errors of the manufactured problem with sigma and with sigma = 0, the same mesh"""
     m, H, levels = util.setup(name, n, div, dim=dim)
     betas, sigmas, rhs, exact = ru.manufactured_problem(H, levels, n, dim, *ru.manufactured2d())
-    x, _ = ru.bicgstab(levels, betas, sigmas, rhs, prolong_util.direct, tol=1e-12, coarse=32)
+    x, _ = vc.bicgstab(levels, betas, rhs, prolong_util.direct, tol=1e-12, sigmas=sigmas, coarse=32)
     betas0, rhs0, exact0 = vc.manufactured_problem(H, levels, n, dim, *vc.manufactured2d())
     x0, _ = vc.bicgstab(levels, betas0, rhs0, prolong_util.direct, tol=1e-12, coarse=32)
     return np.abs(x - exact).max(), np.abs(x0 - exact0).max()
@@ -83,9 +80,6 @@ def test_second_order(name):
     print(f"{name}: max errors (sigma, sigma = 0) {errs}, ratios {ratios}, with sigma = 0 {ratios0}")
     for r, r0 in zip(ratios, ratios0):
         assert abs(r - r0) <= 0.15
-
-
-SOLVES = [("uniform", 8, 3, 2), ("2d2ref.bin", 8, 1, 2), ("uniform", 4, 2, 3), ("2refine.bin", 4, 0, 3)]
 
 
 def sigma_cases(H, n, dim, beta_fn):
@@ -103,8 +97,8 @@ def test_a_larger_diagonal_does_not_cost_iterations(name, n, div, dim, beta_fn):
     _, its0 = vc.bicgstab(levels, betas, b, prolong_util.direct, tol=1e-10, max_it=40, coarse=coarse)
     for kind, sigma0 in sigma_cases(H, n, dim, beta_fn).items():
         sigmas = ru.restrict_all(levels, sigma0)
-        x, its = ru.bicgstab(levels, betas, sigmas, b, prolong_util.direct, tol=1e-10, max_it=40, coarse=coarse)
-        rel = np.linalg.norm(b - ru.apply(levels[0], betas[0], sigmas[0], x)) / np.linalg.norm(b)
+        x, its = vc.bicgstab(levels, betas, b, prolong_util.direct, tol=1e-10, max_it=40, sigmas=sigmas, coarse=coarse)
+        rel = np.linalg.norm(b - vc.apply(levels[0], betas[0], x, sigmas[0])) / np.linalg.norm(b)
         print(f"{name} {dim}d {beta_fn.__name__} {kind}: {its} iterations ({its0} with sigma = 0), true relative residual {rel:.2e}")
         assert rel <= 1e-9
         assert its <= its0, kind
@@ -116,8 +110,8 @@ def test_all_neumann_with_sigma_is_nonsingular(name, n, div, dim):
     betas = vc.restrict_all(levels, vc.beta_from(H.tables(0), n, dim, vc.smooth_beta))
     sigmas = ru.restrict_all(levels, ru.sigma_from(H.tables(0), n, dim, lambda *x: 1.0 + sum(xi * xi for xi in x)))
     f = util.rand_vec(levels[0].size, 6) + 0.5  # (its mean is not zero: the pure Neumann problem would have no solution)
-    x, its = ru.bicgstab(levels, betas, sigmas, f, prolong_util.direct, tol=1e-12, max_it=40, coarse=32 if dim == 2 else 16)
-    r = f - ru.apply(levels[0], betas[0], sigmas[0], x)
+    x, its = vc.bicgstab(levels, betas, f, prolong_util.direct, tol=1e-12, max_it=40, sigmas=sigmas, coarse=32 if dim == 2 else 16)
+    r = f - vc.apply(levels[0], betas[0], x, sigmas[0])
     print(f"{name} {dim}d: {its} iterations, max|f - A x| / max|f| = {np.abs(r).max() / np.abs(f).max():.2e}, mean(x) = {x.mean():.3e}")
     assert its < 40
     assert np.linalg.norm(r) <= 1e-10 * np.linalg.norm(f)

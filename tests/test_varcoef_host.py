@@ -15,6 +15,7 @@ import pytest
 
 from oracle import oracle as orc
 from tests import bc_util, projection_util as pu, prolong_util, util, varcoef_util as vc
+from tests.varcoef_util import SOLVES
 
 MESHES = [("uniform", 4, 2, 3), ("2refine.bin", 4, 0, 3), ("2d2ref.bin", 8, 1, 2), ("uniform", 8, 2, 2)]
 
@@ -90,9 +91,6 @@ def test_second_order(name):
     ratios = [errs[i] / errs[i + 1] for i in range(2)]
     print(f"{name}: max errors {errs}, ratios {ratios}")
     assert min(ratios) >= 3.5
-
-
-SOLVES = [("uniform", 8, 3, 2), ("2d2ref.bin", 8, 1, 2), ("uniform", 4, 2, 3), ("2refine.bin", 4, 0, 3)]
 
 
 @pytest.mark.parametrize("interp", ["direct", "linear"])

@@ -10,18 +10,37 @@ on the lower a-face of each cell; hi[p, a] has the shape of a face: beta on the 
                u_c <- (o - f_c) / d, o = sum_s b_s v_s rh2_a (physical faces 0), d = sum_s b_s kappa_s rh2_a, kappa 1 / 2 (D) / 0 (N)
     jacobi     u + omega (f - A_b u) / (-d_J), d_J = sum_s b_s (1 + adj_s) rh2_a, adj = orc_jacobi's adjustment per side
     restrict_faces   the face average of the 2^(dim-1) fine faces that cover a coarse face; copy-through patches bit for bit
-    cycle / bicgstab GMG/Cycle.h:56-126 and BiCGStab.h:45-106 composed from these, no exact coarse solve"""
+    cycle / bicgstab tests/cycle_util.py's driver (GMG/Cycle.h:56-126, BiCGStab.h:45-106) on these, no exact coarse solve
+
+With `sigma`, a cell vector (tests/reaction_util.py), the same three are A_b - sigma and its sweeps:
+    apply      (A_b u)[c] - sigma_c u_c: A_b exactly as without, then one multiplication and one subtraction
+    rbgs       u_c <- (o - f_c) / (d + sigma_c); colour order and frozen ghosts unchanged
+    jacobi     u + omega (f - (A_b - sigma) u) / (-(d_J + sigma_c))
+and cycle / bicgstab take `sigmas`, one per level, and `sub`, a coefcoarse_util.Sub that solves the coarsest level (section 20).
+
+The last part holds what the tests of the coefficient path share: shapes, random coefficients, downloads of the device's levels."""
+import functools
+
 import numpy as np
+import pytest
 
 from oracle import oracle as orc
-from tests import projection_util as pu
+from pressurepoissonsolver_amd import capi
+from tests import bc_util, cycle_util, projection_util as pu, util
 
 
 def _ax(L, a):
     return L.dim - 1 - a  # numpy axis of coordinate a inside a patch
 
 
-def apply(L, beta, u):
+def _cells(L, v):
+    return np.asarray(v, np.float64).reshape((L.P,) + (L.n,) * L.dim)
+
+
+def apply(L, beta, u, sigma=None):
+    if sigma is not None:
+        u = np.asarray(u, np.float64)
+        return apply(L, beta, u) - np.asarray(sigma, np.float64) * u
     lo, hi = pu.level_grad(L, u)
     return pu.level_div(L, lo * beta[0], hi * beta[1])
 
@@ -62,11 +81,12 @@ def _face_weights(L, p, a, low, high, inner=1.0):
     return w_lo, w_hi
 
 
-def jacobi(L, beta, f, u, omega):
+def jacobi(L, beta, f, u, omega, sigma=None):
     n, D = L.n, L.dim
     _, _, adj = _side_tables(L)
-    r = (np.asarray(f) - apply(L, beta, u)).reshape((L.P,) + (n,) * D)
-    out = np.asarray(u, np.float64).reshape((L.P,) + (n,) * D).copy()
+    r = _cells(L, np.asarray(f) - apply(L, beta, u, sigma))
+    out = _cells(L, u).copy()
+    S = None if sigma is None else _cells(L, sigma)
     for p in range(L.P):
         d = np.zeros((n,) * D)
         for a in range(D):
@@ -75,15 +95,17 @@ def jacobi(L, beta, f, u, omega):
             rh2 = 1.0 / L.a["h"][p, a] ** 2
             d += blo * w_lo * rh2
             d += bhi * w_hi * rh2
+        if S is not None:
+            d = d + S[p]  # the diagonal of A_b - sigma is -(d_J + sigma)
         out[p] += omega * r[p] / (-d)
     return out.ravel()
 
 
-def rbgs(L, beta, f, u):
+def rbgs(L, beta, f, u, sigma=None):
     n, D = L.n, L.dim
     isdir, isneu, _ = _side_tables(L)
-    U = np.asarray(u, np.float64).reshape((L.P,) + (n,) * D)
-    F = np.asarray(f, np.float64).reshape((L.P,) + (n,) * D)
+    U, F = _cells(L, u), _cells(L, f)
+    S = None if sigma is None else _cells(L, sigma)
     gam, ii = orc.interp(L, np.asarray(u, np.float64)), L.iface_index()
     out = U.copy()
     idx = np.indices((n,) * D).sum(axis=0)
@@ -109,6 +131,8 @@ def rbgs(L, beta, f, u):
             ghosts.append(gh)
             bs.append((blo, bhi))
             rh2s.append(rh2)
+        if S is not None:
+            d = d + S[p]  # the one change with sigma: the diagonal of A_b - sigma is -(d + sigma)
         cur = U[p].copy()
         for colour in (0, 1):
             o = np.zeros((n,) * D)
@@ -167,70 +191,31 @@ def restrict_all(levels, beta0):
     return betas
 
 
-def cycle(levels, betas, f, prolong, smoother=2, pre=1, post=1, coarse=1, mid=1, cycle_type=0, omega=6.0 / 7.0):
-    """prolong_util.cycle with A_b and its sweeps; the coarsest level runs `coarse` sweeps of the smoother (no exact solve).
+def operator(levels, betas, sigmas=None, smoother=2, omega=6.0 / 7.0):
+    """-> (apply(l, u), smooth(l, f, u)): A_b (A_b - sigma where sigmas is given) and its sweep on level l, for cycle_util.
     smoother: 1 Jacobi, 2 patch-local RB-GS -- the numbers of TE_SMOOTH_*."""
-    nl = len(levels)
+    sig = lambda l: None if sigmas is None else sigmas[l]
 
     def smooth(l, f, u):
         if smoother == 1:
-            return jacobi(levels[l], betas[l], f, u, omega)
-        return rbgs(levels[l], betas[l], f, u)
+            return jacobi(levels[l], betas[l], f, u, omega, sig(l))
+        return rbgs(levels[l], betas[l], f, u, sig(l))
 
-    def visit(l, f, u):
-        L = levels[l]
-        if l == nl - 1:
-            for _ in range(coarse):
-                u = smooth(l, f, u)
-            return u
-
-        def descend(u):
-            r = -1 * apply(L, betas[l], u) + f
-            cf = orc.restrict(L, levels[l + 1], r)
-            cu = visit(l + 1, cf, np.zeros(levels[l + 1].size))
-            return prolong(L, levels[l + 1], cu, u)
-
-        for _ in range(pre):
-            u = smooth(l, f, u)
-        u = descend(u)
-        if cycle_type == 1:
-            for _ in range(mid):
-                u = smooth(l, f, u)
-            u = descend(u)
-        for _ in range(post):
-            u = smooth(l, f, u)
-        return u
-
-    return visit(0, np.ascontiguousarray(f, np.float64), np.zeros(levels[0].size))
+    return (lambda l, u: apply(levels[l], betas[l], u, sig(l))), smooth
 
 
-def bicgstab(levels, betas, b, prolong, max_it=100, tol=1e-12, **kw):
-    """prolong_util.bicgstab with A_b, right-preconditioned by the composed cycle -> (x, iterations)"""
-    L = levels[0]
-    A = lambda v: apply(L, betas[0], v)
-    M = lambda v: cycle(levels, betas, v, prolong, **kw)
-    x = np.zeros(L.size)
-    resid = -1 * A(x) + b
-    r0 = np.linalg.norm(resid)
-    rhat, p = resid.copy(), resid.copy()
-    rho = rhat @ resid
-    its = 0
-    while np.linalg.norm(resid) / r0 > tol and its < max_it:
-        mp = M(p)
-        ap = A(mp)
-        alpha = rho / (rhat @ ap)
-        s = resid + ap * -alpha
-        ms = M(s)
-        as_ = A(ms)
-        omega = (as_ @ s) / (as_ @ as_)
-        x = x + mp * alpha + ms * omega
-        resid = resid + ap * -alpha + as_ * -omega
-        rho_new = resid @ rhat
-        beta = rho_new * alpha / (rho * omega)
-        p = beta * (p + ap * -omega) + resid
-        its += 1
-        rho = rho_new
-    return x, its
+def cycle(levels, betas, f, prolong, sigmas=None, sub=None, smoother=2, omega=6.0 / 7.0, **kw):
+    """cycle_util.cycle with A_b (- sigma) and its sweeps; the coarsest level runs `coarse` sweeps of the smoother (no exact solve),
+    or the sub-patch solve of a coefcoarse_util.Sub with the same options. kw: pre, post, coarse, mid, cycle_type."""
+    A, smooth = operator(levels, betas, sigmas, smoother, omega)
+    coarsest = None if sub is None else lambda f, u: sub.solve(f, u, prolong, smoother=smoother, omega=omega, **kw)
+    return cycle_util.cycle(levels, f, A, smooth, prolong, coarsest, **kw)
+
+
+def bicgstab(levels, betas, b, prolong, max_it=100, tol=1e-12, sigmas=None, **kw):
+    """cycle_util.bicgstab with A_b (- sigma), right-preconditioned by the cycle above -> (x, iterations). No mean shift anywhere."""
+    A = lambda v: apply(levels[0], betas[0], v, None if sigmas is None else sigmas[0])
+    return cycle_util.bicgstab(A, lambda v: cycle(levels, betas, v, prolong, sigmas=sigmas, **kw), b, max_it, tol)
 
 
 def face_centres(t, n, dim):
@@ -306,6 +291,17 @@ def manufactured2d():
     return beta, u, F
 
 
+def manufactured3d():
+    """beta = exp(x + y + z), u = sin(2x + 0.3) sin(3y + 0.1) sin(1.5z + 0.2), F = div(beta grad u)"""
+    beta = lambda x, y, z: np.exp(x + y + z)
+    sx, sy, sz = (lambda x: np.sin(2 * x + 0.3)), (lambda y: np.sin(3 * y + 0.1)), (lambda z: np.sin(1.5 * z + 0.2))
+    cx, cy, cz = (lambda x: np.cos(2 * x + 0.3)), (lambda y: np.cos(3 * y + 0.1)), (lambda z: np.cos(1.5 * z + 0.2))
+    u = lambda x, y, z: sx(x) * sy(y) * sz(z)
+    F = lambda x, y, z: np.exp(x + y + z) * (-(4 + 9 + 2.25) * u(x, y, z) + 2 * cx(x) * sy(y) * sz(z) + 3 * sx(x) * cy(y) * sz(z)
+                                             + 1.5 * sx(x) * sy(y) * cz(z))
+    return beta, u, F
+
+
 def manufactured_problem(H, levels, n, dim, beta_fn, u_fn, F_fn):
     """-> (betas per level, right-hand side with the boundary terms of the b_beta recipe, exact solution at the cell centres)"""
     L, t = levels[0], H.tables(0)
@@ -328,3 +324,59 @@ def smooth_beta(*x):
 def jump_beta(*x):
     r2 = sum((xi - 0.5) ** 2 for xi in x)
     return np.where(r2 < 0.3 ** 2, 100.0, 1.0)
+
+
+# ---- what the tests of the coefficient path share (test_gpu_varcoef.py, test_gpu_reaction.py, test_gpu_coef_coarse.py and their host tests)
+# (mesh, divides, n, dim): whole-patch path; smallest tile; 8 patches of the production tile; coarse/fine ghosts and copy-through;
+# 2D; 2D refined; the largest 2D patch the LDS form of the sweep takes (test_sweep_above_the_lds_limit: the form above it)
+SHAPES = [("uniform", 2, 8, 3), ("uniform", 1, 4, 3), ("uniform", 1, 32, 3), ("2refine.bin", 1, 8, 3), ("uniform", 3, 8, 2), ("2d2ref.bin", 2, 8, 2),
+          ("uniform", 1, 64, 2)]
+
+
+def masks_of(dim):
+    return (0, (1 << 2 * dim) - 1, bc_util.CHANNEL if dim == 3 else bc_util.MASKS2[0])  # Dirichlet, all-Neumann, mixed
+
+
+CASES = [s + (mask,) for s in SHAPES for mask in masks_of(s[3])]
+# the meshes of the comparisons with the CPU composition, (mesh, n, divides, dim)
+SOLVES = [("uniform", 8, 3, 2), ("2d2ref.bin", 8, 1, 2), ("uniform", 4, 2, 3), ("2refine.bin", 4, 0, 3)]
+
+
+def rel(a, b):
+    return np.linalg.norm(a - b) / np.linalg.norm(b)
+
+
+def random_beta(size, seed):
+    """a packed face vector"""
+    return np.random.default_rng(seed).uniform(0.5, 2.0, size)
+
+
+def random_beta_faces(L, seed):
+    """(lo, hi) of level L"""
+    rng = np.random.default_rng(seed)
+    return rng.uniform(0.5, 2.0, (L.P, L.dim) + (L.n,) * L.dim), rng.uniform(0.5, 2.0, (L.P, L.dim) + (L.n,) * (L.dim - 1))
+
+
+def device_betas(g, levels, n, dim):
+    """the solver's coefficient on every level, downloaded -> [(lo, hi)]"""
+    out = []
+    for l in range(len(levels)):
+        v = g.new_face_vector(l)
+        g.coefficient(l, v)
+        out.append(pu.unpack(v.download(), n, dim))
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def solve_setup(name, n, div, dim):
+    """one hierarchy and one solver per mesh, shared by the tests that leave it as they found it"""
+    m, H, levels = util.setup(name, n, div, dim=dim)
+    return H, levels, capi.GMG(H)
+
+
+def refused(call, code, word=None):
+    with pytest.raises(capi.TeError) as e:
+        call()
+    assert e.value.code == code, str(e.value)
+    if word is not None:
+        assert word in str(e.value), str(e.value)
