@@ -784,6 +784,45 @@ int te_faces_from_cells(te_gmg *g, int level, int mode, const te_vec *c, const t
 int te_project_weighted(te_gmg *g, int level, double alpha, const te_vec *p, const te_vec *bdata, const te_vec *w, te_vec *U);
 int te_add_boundary_rhs_weighted(te_gmg *g, int level, const te_vec *bdata, const te_vec *w, te_vec *f);
 
+/* Transport of a cell field by a face velocity on the device: rho^{n+1} = rho^n - dt div(U rho) with the projected velocity U, first
+ * order upwind (donor cell), conservative on refined meshes. The four calls work on every level, in 2D and 3D, and are additive: none
+ * reads or changes the solver's coefficient, reaction term, interpolator or options, and a te_vcycle or te_bicgstab afterwards gives the
+ * bits it gave before. Single rank: TE_ESTATE (the message says "sharded") on a sharded hierarchy.
+ *
+ * te_advect_flux(g, level, U, c, cb, F): F = U (.) c_upwind. U, F = distinct face vectors of `level`, c = a domain vector, cb = a
+ * boundary vector of `level` or NULL. Every entry has one writer, no atomics. A face has two operands, lo on its lower-coordinate side
+ * and hi on its upper side, and with U = this patch's own stored entry of the face
+ *     s = (U >= 0.0) ? lo : hi,   F = U * s.
+ *   interior face, patch face with a same-level neighbour: the two adjacent cells, the neighbour's read in place (te_faces_from_cells'
+ *     operands); both stored copies of such a face receive the same bits when U's copies agree.
+ *   physical face (Dirichlet and Neumann alike): outside the domain stands cb's entry for that face point where cb is given, else the
+ *     cell just inside; inside stands that cell. Inflow carries the datum, outflow the cell's own value.
+ *   coarse/fine face, fine side: the other operand is the coarse neighbour's cell that covers the face (te_faces_from_cells' rule), the
+ *     entry is formed as above with the fine copy of U.
+ *   coarse/fine face, coarse side: ((F00 + F10) + (F01 + F11)) * 0.25 (2D: (F0 + F1) * 0.5) of the fine-side fluxes of the fine faces
+ *     that cover the coarse face, first index along the face's lower remaining axis. They are formed from the fine patches' own copies
+ *     of U, their facing-layer cells and this coarse cell -- the operands and the expression of the fine side -- so the coarse copy
+ *     equals the mean of the fine copies BIT FOR BIT: te_divergence(F) telescopes across the face. The coarse copy of U there is never
+ *     read.
+ * TE_EINVAL: NULL (U, c, F), a vector of the wrong kind, level or solver, F aliases U.
+ *
+ * te_advect(g, level, alpha, U, c, cb, out): out = c - alpha div(U c_upwind) in one pass, the flux never stored. out = a domain vector
+ * distinct from c. The bits are those of the composition te_advect_flux -> F, d = te_divergence(alpha, F), te_vec_copy(out, c),
+ * te_vec_add_scaled(out, -1.0, d). With alpha * dim * rate <= 1 (rate: te_faces_max_rate of U) and c, cb >= 0 the result is >= 0.
+ * TE_EINVAL: NULL (U, c, out), wrong kinds, levels or solvers, out aliases c.
+ *
+ * te_faces_match(g, level, F): on every coarse/fine face the coarse side's stored entries become the mean of the covering fine copies
+ * (the association above); everything else is untouched. One writer per entry, no atomics. Afterwards te_divergence(F) telescopes across
+ * coarse/fine faces -- for any face field, e.g. a projected velocity before it transports something. Idempotent; te_advect_flux's
+ * output is a fixed point, bit for bit. TE_EINVAL: NULL, not a face vector of the level.
+ *
+ * te_faces_max_rate(g, level, U, rate): *rate = the maximum over all stored entries of |U_a| / h_a, h_a the owning patch's spacing
+ * (0 on a level without patches). Synchronises the solver stream. TE_EINVAL: NULL, not a face vector of the level. */
+int te_advect_flux(te_gmg *g, int level, const te_vec *U, const te_vec *c, const te_vec *cb, te_vec *F);
+int te_advect(te_gmg *g, int level, double alpha, const te_vec *U, const te_vec *c, const te_vec *cb, te_vec *out);
+int te_faces_match(te_gmg *g, int level, te_vec *F);
+int te_faces_max_rate(te_gmg *g, int level, const te_vec *U, double *rate);
+
 /* kernel timing hooks for bench.py: HIP-event time of the last te_vcycle's dominant kernel */
 int te_gmg_profile(te_gmg *g, int enable);
 /* name[i] (<=63 chars), calls[i], total_ms[i] (HIP events on the solver stream), cells[i]

@@ -179,6 +179,10 @@ SYMBOLS = {
     "te_faces_from_cells": (_I, [_P, _I, _I, _P, _P, _P]),
     "te_project_weighted": (_I, [_P, _I, _D, _P, _P, _P, _P]),
     "te_add_boundary_rhs_weighted": (_I, [_P, _I, _P, _P, _P]),
+    "te_advect_flux": (_I, [_P, _I, _P, _P, _P, _P]),
+    "te_advect": (_I, [_P, _I, _D, _P, _P, _P, _P]),
+    "te_faces_match": (_I, [_P, _I, _P]),
+    "te_faces_max_rate": (_I, [_P, _I, _P, _PD]),
     "te_faces_restrict": (_I, [_P, _I, _P, _P]),
     "te_gmg_set_coefficient": (_I, [_P, _P]),
     "te_gmg_has_coefficient": (_I, [_P]),
@@ -622,6 +626,25 @@ class GMG:
     def add_boundary_rhs_weighted(self, bdata, w, f, level=0):
         """add_boundary_rhs with every datum multiplied first by the face weight w on its physical face, in place"""
         check(lib().te_add_boundary_rhs_weighted(self.h, level, bdata.h, w.h, f.h))
+
+    # ---- transport of a cell field by a face velocity (te_hip.h te_advect_flux): donor-cell flux, update, matching, rate. Single rank.
+    def advect_flux(self, U, c, F, cb=None, level=0):
+        """F = U (.) c_upwind, matched on coarse/fine faces; cb: the field's values on the physical faces (None: the cell just inside)"""
+        check(lib().te_advect_flux(self.h, level, U.h, c.h, cb.h if cb is not None else None, F.h))
+
+    def advect(self, U, c, out, alpha=1.0, cb=None, level=0):
+        """out = c - alpha div(U c_upwind) in one pass, out distinct from c"""
+        check(lib().te_advect(self.h, level, float(alpha), U.h, c.h, cb.h if cb is not None else None, out.h))
+
+    def faces_match(self, F, level=0):
+        """the coarse side's entries of every coarse/fine face <- the mean of the covering fine copies, in place"""
+        check(lib().te_faces_match(self.h, level, F.h))
+
+    def faces_max_rate(self, U, level=0):
+        """max |U_a| / h_a over the stored entries of the face vector U"""
+        r = C.c_double(0.0)
+        check(lib().te_faces_max_rate(self.h, level, U.h, C.byref(r)))
+        return r.value
 
     # ---- the variable-coefficient operator div(beta grad u) (te_hip.h: a second path, taken while a coefficient is set)
     def set_coefficient(self, beta):

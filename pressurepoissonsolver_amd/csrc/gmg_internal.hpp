@@ -17,6 +17,7 @@
 //   gmg_faceregrid.hip the transfer of a face vector between two meshes te_faces_regrid (faceregridkernels.hpp)
 //   gmg_coef.hip       the variable-coefficient operator div(beta grad u): coefficient per level, operator, sweeps, cycle (coefkernels.hpp)
 //   gmg_density.hip    the variable-density step around it: te_faces_from_cells, te_project_weighted, te_add_boundary_rhs_weighted (densitykernels.hpp)
+//   gmg_advect.hip     transport of a cell field by a face velocity: te_advect_flux, te_advect, te_faces_match, te_faces_max_rate (advectkernels.hpp)
 //   gmg_coefcoarse.hip its sub-patch coarse solve te_gmg_set_coef_coarse: the auxiliary solver on the split tree (coefcoarsekernels.hpp)
 #pragma once
 #include "capi_common.hpp"
@@ -110,7 +111,11 @@ enum KClass : int {
 	KC_COEF_SPLIT, KC_COEF_MERGE,
 	// the variable-density step (densitykernels.hpp): face coefficients from a cell field (34.25 B per site at 32^3), the weighted
 	// projection (83.75), the fold of boundary data under a face weight (cells = boundary values)
-	KC_FACES_FROM_CELLS, KC_PROJECT_WEIGHTED, KC_BOUNDARY_RHS_W, KC_COUNT
+	KC_FACES_FROM_CELLS, KC_PROJECT_WEIGHTED, KC_BOUNDARY_RHS_W,
+	// transport of a cell field by a face velocity (advectkernels.hpp): the donor-cell flux (59 B per site at 32^3), the update
+	// c - alpha div(U c_upwind) in one pass (42.25), the matching of a face vector across coarse/fine faces (cells = coarse/fine face
+	// entries) and the largest |U_a| / h_a (cells = face-vector entries, 8 B each)
+	KC_ADVECT_FLUX, KC_ADVECT, KC_FACES_MATCH, KC_FACES_RATE, KC_COUNT
 };
 extern const char *kclassName[KC_COUNT]; // (gmg_core.hip)
 
