@@ -823,6 +823,46 @@ int te_advect(te_gmg *g, int level, double alpha, const te_vec *U, const te_vec 
 int te_faces_match(te_gmg *g, int level, te_vec *F);
 int te_faces_max_rate(te_gmg *g, int level, const te_vec *U, double *rate);
 
+/* Second-order limited (MUSCL) transport: te_advect_flux / te_advect with the cell operands of a face replaced by edge states formed
+ * from limited slopes. Every level, 2D and 3D, additive like the calls above; single rank: TE_ESTATE ("sharded")
+ * on a sharded hierarchy. Every operation below is rounded on its own.
+ *
+ * Slope of a cell along axis a: dm = c - m and dp = p - c, with m and p the operands beyond the cell's lower and upper a-face. The
+ * operand beyond a face is exactly te_faces_from_cells' and te_advect_flux's: the same-level neighbour's facing cell; on a physical
+ * face the boundary vector's entry, or without cb the cell itself; the covering coarse cell, raw, where the neighbour is coarser; the
+ * average ((f00 + f10) + (f01 + f11)) * 0.25 (2D (f0 + f1) * 0.5) of the covering fine cells where the neighbours are finer.
+ *   TE_SLOPE_ZERO (0)      S = 0.0
+ *   TE_SLOPE_MINMOD (1)    S = (dm*dp > 0.0) ? (fabs(dm) < fabs(dp) ? dm : dp) : 0.0
+ *   TE_SLOPE_MC (2)        t = 0.5*(dm + dp), w = fmin(fmin(2.0*fabs(dm), 2.0*fabs(dp)), fabs(t)), S = (dm*dp > 0.0) ? copysign(w, dm) : 0.0
+ *   TE_SLOPE_CENTRAL (3)   S = 0.5*(dm + dp). Unlimited, no positivity guarantee: for smooth fields, and the tests' negative control.
+ *
+ * Flux of a face: te_advect_flux's rule, s = (U >= 0.0) ? lo : hi, F = U * s, with the cell operands replaced by edge states. A cell
+ * on the lower side of the face contributes lo = c + 0.5*S_a, a cell on the upper side hi = c - 0.5*S_a. An operand that is not a cell
+ * of this level enters as it is: the boundary datum, the own cell standing in for it, the raw coarse cell on the fine side of a
+ * coarse/fine face, and the coarse cell on the coarse side.
+ *   same-level interior face: both sides are edge states; the two patches' copies get the same bits when U's copies agree.
+ *   coarse/fine face, fine side: upwindFlux(U_f, C, m - 0.5*S) on a lower face, upwindFlux(U_f, m + 0.5*S, C) on an upper one; C the
+ *     covering coarse cell, m the fine facing cell, S its slope along the face's axis.
+ *   coarse/fine face, coarse side: the mean (te_advect_flux's association) of those same fine-side values, formed from the fine patch's
+ *     own U, m, S and this C: the coarse copy equals the mean of the fine copies bit for bit. The coarse copy of U is never read.
+ * The scheme is first order at coarse/fine and physical faces and second order elsewhere.
+ *
+ * te_cell_slopes(g, level, kind, c, cb, sx, sy, sz): the slopes of c along x, y, z. sx, sy, sz = distinct domain vectors of `level`,
+ * none aliasing c; sz is NULL in 2D and required in 3D. c is read once.
+ * te_advect_flux_muscl(g, level, kind, U, c, cb, F), te_advect_muscl(g, level, alpha, kind, U, c, cb, out): te_advect_flux's and
+ * te_advect's arguments and refusals, plus TE_EINVAL for an unknown kind. The slopes live in vectors the solver owns per level, made at
+ * first use and freed by te_gmg_release_workspace and te_gmg_destroy. te_advect_muscl's bits are those of te_advect_flux_muscl -> F,
+ * d = te_divergence(alpha, F), te_vec_copy(out, c), te_vec_add_scaled(out, -1.0, d). With TE_SLOPE_ZERO both give te_advect_flux's and
+ * te_advect's values. For ZERO, MINMOD and MC, with c, cb >= 0 and ANY U: alpha * 2 * dim * rate <= 1 keeps the result >= 0 on a level
+ * without coarse/fine faces, alpha * 2.5 * dim * rate <= 1 on one with them (rate: te_faces_max_rate of U). */
+#define TE_SLOPE_ZERO    0
+#define TE_SLOPE_MINMOD  1
+#define TE_SLOPE_MC      2
+#define TE_SLOPE_CENTRAL 3
+int te_cell_slopes(te_gmg *g, int level, int kind, const te_vec *c, const te_vec *cb, te_vec *sx, te_vec *sy, te_vec *sz);
+int te_advect_flux_muscl(te_gmg *g, int level, int kind, const te_vec *U, const te_vec *c, const te_vec *cb, te_vec *F);
+int te_advect_muscl(te_gmg *g, int level, double alpha, int kind, const te_vec *U, const te_vec *c, const te_vec *cb, te_vec *out);
+
 /* kernel timing hooks for bench.py: HIP-event time of the last te_vcycle's dominant kernel */
 int te_gmg_profile(te_gmg *g, int enable);
 /* name[i] (<=63 chars), calls[i], total_ms[i] (HIP events on the solver stream), cells[i]

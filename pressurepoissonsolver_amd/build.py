@@ -32,7 +32,7 @@ def hipcc():
 
 
 # translation units of libte_hip.so (gmg_internal.hpp says what lives where); compiled in parallel, one object file each
-UNITS = ("gmg_core.hip", "gmg_transport.hip", "gmg_launch3d.hip", "gmg_fused3d.hip", "gmg_patchsolve.hip", "gmg_launch2d.hip", "gmg_cycle.hip", "gmg_krylov.hip", "gmg_schur.hip", "gmg_bc.hip", "gmg_projection.hip", "gmg_prolong.hip", "gmg_fmg.hip", "gmg_regrid.hip", "gmg_faceregrid.hip", "gmg_coef.hip", "gmg_coefcoarse.hip", "gmg_density.hip", "gmg_advect.hip", "capi_mesh.cpp", "mesh.cpp", "level_tables.cpp")
+UNITS = ("gmg_core.hip", "gmg_transport.hip", "gmg_launch3d.hip", "gmg_fused3d.hip", "gmg_patchsolve.hip", "gmg_launch2d.hip", "gmg_cycle.hip", "gmg_krylov.hip", "gmg_schur.hip", "gmg_bc.hip", "gmg_projection.hip", "gmg_prolong.hip", "gmg_fmg.hip", "gmg_regrid.hip", "gmg_faceregrid.hip", "gmg_coef.hip", "gmg_coefcoarse.hip", "gmg_density.hip", "gmg_advect.hip", "gmg_muscl.hip", "capi_mesh.cpp", "mesh.cpp", "level_tables.cpp")
 CFLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-result", "-Wno-unused-function"]
 
 

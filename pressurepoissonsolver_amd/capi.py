@@ -33,6 +33,7 @@ SCHUR_PREC_NONE, SCHUR_PREC_CHEB = 0, 1
 INTERP_DIRECT, INTERP_LINEAR = 0, 1  # TE_INTERP_*: DrctIntp (the default), tri-/bilinear
 SLABS_STENCIL, SLABS_SWEEP = 0, 1  # TE_SLABS_*: which slab rule te_gmg_slab_count reports
 FACE_MEAN, FACE_HARMONIC, FACE_RECIP_MEAN = 0, 1, 2  # TE_FACE_*: how te_faces_from_cells combines the two operands of a face
+SLOPE_ZERO, SLOPE_MINMOD, SLOPE_MC, SLOPE_CENTRAL = 0, 1, 2, 3  # TE_SLOPE_*: the slope kinds of te_cell_slopes / te_advect_muscl
 COEF_COARSE_SWEEPS, COEF_COARSE_SUBCYCLE = 0, 1  # TE_COEF_COARSE_*: the coarsest level of the cycle with a coefficient
 
 
@@ -183,6 +184,9 @@ SYMBOLS = {
     "te_advect": (_I, [_P, _I, _D, _P, _P, _P, _P]),
     "te_faces_match": (_I, [_P, _I, _P]),
     "te_faces_max_rate": (_I, [_P, _I, _P, _PD]),
+    "te_cell_slopes": (_I, [_P, _I, _I, _P, _P, _P, _P, _P]),
+    "te_advect_flux_muscl": (_I, [_P, _I, _I, _P, _P, _P, _P]),
+    "te_advect_muscl": (_I, [_P, _I, _D, _I, _P, _P, _P, _P]),
     "te_faces_restrict": (_I, [_P, _I, _P, _P]),
     "te_gmg_set_coefficient": (_I, [_P, _P]),
     "te_gmg_has_coefficient": (_I, [_P]),
@@ -645,6 +649,20 @@ class GMG:
         r = C.c_double(0.0)
         check(lib().te_faces_max_rate(self.h, level, U.h, C.byref(r)))
         return r.value
+
+    # ---- second-order limited (MUSCL) transport (te_hip.h te_cell_slopes): slopes, flux from edge states, update. Single rank.
+    def cell_slopes(self, c, sx, sy, sz=None, kind=SLOPE_MC, cb=None, level=0):
+        """sx, sy, sz = the slopes of the cell field c along x, y, z (SLOPE_ZERO, SLOPE_MINMOD, SLOPE_MC or SLOPE_CENTRAL); sz is
+        None in 2D"""
+        check(lib().te_cell_slopes(self.h, level, int(kind), c.h, cb.h if cb is not None else None, sx.h, sy.h, sz.h if sz is not None else None))
+
+    def advect_flux_muscl(self, U, c, F, kind=SLOPE_MC, cb=None, level=0):
+        """advect_flux with the cell operands replaced by the edge states c +- 0.5 S of limited slopes"""
+        check(lib().te_advect_flux_muscl(self.h, level, int(kind), U.h, c.h, cb.h if cb is not None else None, F.h))
+
+    def advect_muscl(self, U, c, out, alpha=1.0, kind=SLOPE_MC, cb=None, level=0):
+        """out = c - alpha div(F), F = advect_flux_muscl's flux, never stored; out distinct from c"""
+        check(lib().te_advect_muscl(self.h, level, float(alpha), int(kind), U.h, c.h, cb.h if cb is not None else None, out.h))
 
     # ---- the variable-coefficient operator div(beta grad u) (te_hip.h: a second path, taken while a coefficient is set)
     def set_coefficient(self, beta):

@@ -466,7 +466,7 @@ __device__ __forceinline__ double faceCell2d(const Level2D &L, const FaceGeom &f
 	const double o = ghost2d(L, c, p, s, t, m, false); // the neighbour's cell or the ghost slot
 	return (s & 1) ? faceValue(mode, m, o) : faceValue(mode, o, m);
 }
-__global__ __launch_bounds__(256) void k_cellface2d(Level2D L, FaceGeom fg, const double *__restrict__ c, double *__restrict__ F, int mode)
+static __global__ __launch_bounds__(256) void k_cellface2d(Level2D L, FaceGeom fg, const double *__restrict__ c, double *__restrict__ F, int mode)
 {
 	const int    n = L.n, h = n / 2;
 	const size_t total = (size_t) L.P * n * h, FV = 2 * (size_t) n * n + 2 * n;
@@ -495,7 +495,7 @@ __global__ __launch_bounds__(256) void k_cellface2d(Level2D L, FaceGeom fg, cons
 }
 
 // k_gradient2d<true> with the weight: w is read where U is
-__global__ __launch_bounds__(256) void k_wproject2d(Level2D L, FaceGeom fg, const double *__restrict__ u, const double *__restrict__ w, double *U,
+static __global__ __launch_bounds__(256) void k_wproject2d(Level2D L, FaceGeom fg, const double *__restrict__ u, const double *__restrict__ w, double *U,
                                                     double alpha)
 {
 	const int    n = L.n, h = n / 2;

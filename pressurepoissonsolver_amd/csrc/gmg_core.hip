@@ -14,7 +14,8 @@ const char *kclassName[KC_COUNT] = {"stencil_apply", "stencil_resid", "stencil_j
                                     "apply_coef", "resid_coef", "jacobi_coef", "rbgs_coef", "faces_restrict",
                                     "coef_split", "coef_merge",
                                     "faces_from_cells", "project_weighted", "boundary_rhs_w",
-                                    "advect_flux", "advect", "faces_match", "faces_max_rate"};
+                                    "advect_flux", "advect", "faces_match", "faces_max_rate",
+                                    "cell_slopes", "advect_flux_muscl", "advect_muscl"};
 const char *optName[O_COUNT] = {"TE_2D_SIMPLE", "TE_2D_NO_MFMA", "TE_2D_NO_PF", "TE_2D_NO_MR_FUSE", "TE_2D_TPB", "TE_NO_FUSE2", "TE_NO_FUSE3",
                                 "TE_NO_FUSE3_CF", "TE_NO_CFP", "TE_NO_XF", "TE_NO_FCORR", "TE_NO_FCORR_CF", "TE_NO_OVERLAP",
                                 "TE_OVERLAP_MIN", "TE_NO_PS_FACES", "TE_PS_MODE", "TE_PS_SLOW", "TE_RBGS_NOSLAB", "TE_ZS_FORCE", "TE_NO_ZS8",
@@ -623,6 +624,8 @@ int te_gmg_release_workspace(te_gmg *g)
 			fmgFree(g);
 			coefRelease(g); // (a coefficient or a reaction term that is set stays: the solver's operator depends on it)
 			coefCoarseRelease(g); // (the auxiliary solver goes while the kind is TE_COEF_COARSE_SWEEPS, else it stays)
+			for (auto &L : g->levels) // the slope vectors of te_advect_flux_muscl / te_advect_muscl
+				for (auto &s : L->muscl_s) (void) s.alloc(0);
 			return TE_OK;
 	});
 }

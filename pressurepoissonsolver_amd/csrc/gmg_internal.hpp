@@ -18,6 +18,7 @@
 //   gmg_coef.hip       the variable-coefficient operator div(beta grad u): coefficient per level, operator, sweeps, cycle (coefkernels.hpp)
 //   gmg_density.hip    the variable-density step around it: te_faces_from_cells, te_project_weighted, te_add_boundary_rhs_weighted (densitykernels.hpp)
 //   gmg_advect.hip     transport of a cell field by a face velocity: te_advect_flux, te_advect, te_faces_match, te_faces_max_rate (advectkernels.hpp)
+//   gmg_muscl.hip      its second-order limited form: te_cell_slopes, te_advect_flux_muscl, te_advect_muscl (musclkernels.hpp)
 //   gmg_coefcoarse.hip its sub-patch coarse solve te_gmg_set_coef_coarse: the auxiliary solver on the split tree (coefcoarsekernels.hpp)
 #pragma once
 #include "capi_common.hpp"
@@ -115,7 +116,10 @@ enum KClass : int {
 	// transport of a cell field by a face velocity (advectkernels.hpp): the donor-cell flux (59 B per site at 32^3), the update
 	// c - alpha div(U c_upwind) in one pass (42.25), the matching of a face vector across coarse/fine faces (cells = coarse/fine face
 	// entries) and the largest |U_a| / h_a (cells = face-vector entries, 8 B each)
-	KC_ADVECT_FLUX, KC_ADVECT, KC_FACES_MATCH, KC_FACES_RATE, KC_COUNT
+	KC_ADVECT_FLUX, KC_ADVECT, KC_FACES_MATCH, KC_FACES_RATE,
+	// second-order limited transport (musclkernels.hpp): the slopes of a cell field (33.5 B per site at 32^3), the flux march from edge
+	// states (84.5) and the update in one pass (67.75); the two marches' entry points run the slope pass first
+	KC_CELL_SLOPES, KC_ADVECT_FLUX_MUSCL, KC_ADVECT_MUSCL, KC_COUNT
 };
 extern const char *kclassName[KC_COUNT]; // (gmg_core.hip)
 
@@ -331,6 +335,7 @@ struct LevelHost {
 	DevBuf<double>  geom_starts, geom_h; // [P][3] lower corner and spacings (te_init_problem)
 	DevBuf<int32_t> node_ids;            // [P] tree node ids
 	DevBuf<double> cellvol;          // [P] product of the spacings (te_integrate)
+	DevBuf<double> muscl_s[3];       // [P][n^dim] each: the slopes of te_advect_flux_muscl / te_advect_muscl, made at first use (gmg_muscl.hip)
 	std::vector<double> patch_vol;   // [P] product of the patch lengths (te_volume)
 	DevBuf<double> f6buf;            // [P][6][n^2]: the six face layers of an iterate that is never stored (opts.fuse = 3)
 	// Where the RB-GS kernels keep face layer (p, s) inside f6buf (LevelDev.f6off): the layers that travel to other ranks
